@@ -28,6 +28,13 @@ Launch: under torchrun (RANK / WORLD_SIZE set) every process is one rank.
 `--gpus N > 1` without torchrun starts the N ranks itself, as a torchrun child
 process, before this process touches the GPU, and relays rank 0's line.
 
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, write the outputs if --dump-outputs is given, print the line
+(value, ms_per_step, and the roofline / breakdown read from the timed steps'
+own events). Everything that takes runs of its own -- the round trip, the
+box's copy rate, the pair sweep, the XOR leg, the sharded leg and the CPU
+baselines -- runs under --full, each still switched by its own option.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -85,7 +92,17 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl",
                     help="process-group backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg and check (round trip, copy probe, "
+                         "--pairs, --xor, --sharded, --cpu-baseline); without it none of them runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float32): "
+                         "parity = every member's parity cells, rebuilt = the lost members' data and parity cells; "
+                         "cells too large for the budget are sampled at fixed, seeded offsets")
+    args = ap.parse_args()
+    if not args.full:
+        args.cpu_baseline = args.sharded = args.xor = args.pairs = 0
+    return args
 
 
 def _host_random(n, rng):
@@ -250,6 +267,19 @@ def cell_pad(args, chunk):
     return redset_amd.cell_stride(chunk) - -(-chunk // 256) * 256
 
 
+def fill_set(lay, seed):
+    """The timed set's inputs: every member's logical file filled with
+    uniform random bytes from a device generator seeded with `seed`, so the
+    same arguments give the same inputs in every run."""
+    import torch
+
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    for r in range(lay.ranks):
+        n = lay.lofi(r).numel()
+        lay.lofi(r).copy_(torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda", generator=g))
+
+
 def timed(step, steps, warmup, dist_on, before=None):
     """W untimed warmups, then K steps bracketed by barrier + synchronize on
     both sides; returns the max-over-ranks elapsed seconds."""
@@ -298,6 +328,46 @@ def round_trip(lay, enc_plan, reb_plan, lost, stream):
     reb_plan.execute(stream)
     torch.cuda.synchronize()
     return all(torch.equal(c, s) for c, s in zip(cells, snap))
+
+
+DUMP_BUDGET_BYTES = 32 * MIB  # float32 bytes over all dumped arrays (the option's limit is 64 MB)
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirpath, lay, lost, rank, world):
+    """--dump-outputs: what the last timed step left in the set, as float32
+    .npy files, one row per cell. `parity`: the encode's output, the e parity
+    cells of every member (member-major); `rebuilt`: the rebuild's output,
+    the lost members' d data cells then e parity cells (member-major). Cells
+    that fit the budget are written whole; else every cell is sampled at its
+    own offsets drawn once from a fixed seed (the same in every run and
+    build), with replacement. N > 1: each rank writes its own set, the name
+    suffixed _rank<r>."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize()
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {
+        "parity": [lay.parity_cell(r, i) for r in range(lay.ranks) for i in range(lay.parity_cells)],
+        "rebuilt": [c for r in lost for c in
+                    [lay.data_cell(r, s) for s in range(lay.data_cells)] +
+                    [lay.parity_cell(r, i) for i in range(lay.parity_cells)]],
+    }
+    per_array = DUMP_BUDGET_BYTES // 4 // len(arrays)  # float32 elements
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, cells in arrays.items():
+        if not cells:
+            continue
+        n = cells[0].numel()
+        per_cell = min(n, per_array // len(cells))
+        out = np.empty((len(cells), per_cell), np.float32)
+        for k, c in enumerate(cells):
+            if per_cell < n:
+                idx = torch.from_numpy(rng.integers(0, n, per_cell)).to(c.device)
+                c = c[idx]
+            out[k] = c.cpu().numpy()
+        np.save(os.path.join(dirpath, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), out)
 
 
 def copy_probe(stream, nbytes=1 << 30, reps=10):
@@ -801,12 +871,8 @@ def main():
     # this rank's own set, all cells resident in HBM
     codec = redset_amd.RSCodec(p, e)
     lay = redset_amd.SetLayout.allocate(p, d, e, chunk, pad=cell_pad(args, chunk))
-    g = torch.Generator(device="cuda")
-    g.manual_seed(1234 + rank)
-    for r in range(p):
-        n = lay.lofi(r).numel()
-        lay.lofi(r).copy_(torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda", generator=g))
-    enc_plan = codec.plan_encode(lay.lofi_ptrs(), lay.parity_ptrs(), chunk, lay.cell_stride)
+    fill_set(lay, 1234 + rank)
+    enc_plan =codec.plan_encode(lay.lofi_ptrs(), lay.parity_ptrs(), chunk, lay.cell_stride)
     reb_plan = codec.plan_rebuild(lost, lay.lofi_ptrs(), lay.parity_ptrs(), chunk, lay.cell_stride)
     eb = enc_plan.bytes_read + enc_plan.bytes_written
     rb = reb_plan.bytes_read + reb_plan.bytes_written
@@ -825,19 +891,23 @@ def main():
 
     elapsed = timed(step, args.steps, args.warmup, dist_on)
     ms_per_step = elapsed * 1e3 / args.steps
-    # after the timed region: the round trip on this rank's set, and the box's copy rate
-    rt_ok = round_trip(lay, enc_plan, reb_plan, lost, stream)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lay, lost, rank, world)
+    # after the timed region (--full): the round trip on this rank's set, and the box's copy rate
+    rt_ok = round_trip(lay, enc_plan, reb_plan, lost, stream) if args.full else None
     # every launch so far (timed steps included) completed its loader-ring handshakes
     ring_faults = redset_amd.ring_faults()
     # no kernel wait without a fallback gave up (include/redset_hip.h
     # redset_hip_hang_faults): a nonzero count means wrong bytes somewhere
     hang_faults = redset_amd.hang_faults()
-    rt_ok = rt_ok and ring_faults == 0 and hang_faults == 0
-    if dist_on:
-        flag = torch.tensor([int(rt_ok)], dtype=torch.int32, device="cuda" if args.dist_backend == "nccl" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        rt_ok = bool(flag.item())
-    box_copy = copy_probe(stream)
+    if args.full:
+        rt_ok = rt_ok and ring_faults == 0 and hang_faults == 0
+        if dist_on:
+            flag = torch.tensor([int(rt_ok)], dtype=torch.int32,
+                                device="cuda" if args.dist_backend == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            rt_ok = bool(flag.item())
+    box_copy = copy_probe(stream) if args.full else None
     value = world * bytes_per_step / (elapsed / args.steps) / 1e9
 
     result = {
@@ -916,14 +986,18 @@ def main():
         "step_event_ms": {"median": round(step_ms_median, 4), "min": round(min(step_ms), 4),
                           "max": round(max(step_ms), 4)},
     }
-    result["round_trip_bit_exact"] = rt_ok
+    result["full"] = bool(args.full)
     result["ring_faults"] = ring_faults
     result["hang_faults"] = hang_faults
-    result["box_reference"] = {
-        "torch_copy_GBps": box_copy,
-        "codec_vs_copy": round(achieved / box_copy, 4),
-        "note": "same box, same process: device-to-device copy of 1 GiB (read + write bytes)",
-    }
+    if args.full:
+        result["round_trip_bit_exact"] = rt_ok
+        result["box_reference"] = {
+            "torch_copy_GBps": box_copy,
+            "codec_vs_copy": round(achieved / box_copy, 4),
+            "note": "same box, same process: device-to-device copy of 1 GiB (read + write bytes)",
+        }
+    if args.dump_outputs:
+        result["dumped_outputs"] = args.dump_outputs
     if args.pairs and rank == 0:
         result["rebuild_every_pair"] = rebuild_pairs(codec, lay, chunk, stream)
     if args.xor and rank == 0:

@@ -9,8 +9,8 @@
  * reedsolomon.c:826-1006, src/redset_xor.c:560-671) open the lost members'
  * files for writing, rewrite their headers and call the decode slot.
  *
- * Test infrastructure, built only where the reference's headers exist (this
- * container; tests/adapter/Makefile): redset_base, redset_reedsolomon and
+ * Test infrastructure, built only where the reference's headers exist
+ * (oracle/adapter_test.mk): redset_base, redset_reedsolomon and
  * redset_lofi are the reference's own types. Three reference symbols the
  * adapter uses are defined here, test-only, as restatements:
  *   redset_lofi_pread / redset_lofi_pwrite -- src/redset_lofi.c:424-451 over

@@ -11,8 +11,8 @@ redset_lofi_pread / pwrite, src/redset_lofi.c:424-451), restated test-only
 in the driver with the reference's padding rules. The parity after each
 header and the rebuilt files are compared with the oracle.
 
-The driver is built where the reference's headers exist (this container,
-tests/adapter/Makefile) and travels to the GPU box prebuilt.
+The driver is built where the reference's headers exist (oracle/adapter_test.mk,
+into oracle/_ref/, which is not in git) and travels to the GPU machine prebuilt.
 """
 import os
 
@@ -25,7 +25,7 @@ from test_gpu_mpi import MPIRUN, _have, _logical, _manifests, _setup
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "adapter", "build", "adapter_test")
+DRIVER = os.path.join(ROOT, "oracle", "_ref", "adapter_test")
 
 
 def _run(np_, args, env=None, timeout=240):
@@ -36,7 +36,8 @@ def _run(np_, args, env=None, timeout=240):
 def _need():
     if not _have():
         pytest.skip("needs a GPU and MPICH")
-    assert os.path.exists(DRIVER), f"{DRIVER} missing: build it with `make -C tests/adapter` (needs the reference headers)"
+    assert os.path.exists(DRIVER), (f"{DRIVER} missing: __graft_entry__.build() makes it where the reference's "
+                                    "headers are (oracle/adapter_test.mk)")
 
 
 @pytest.mark.parametrize("exchange", ["auto", "sharded-mpi", "sharded-host"])

@@ -8,7 +8,10 @@
 * `--gpus 1`: the sharded leg runs at N=1 over the world-1 RCCL transport
   (configs[3]'s base point) and is bit-exact.
 Small chunks keep both runs to seconds (gloo moves device tensors at tens of
-MB/s); the CPU baseline, pair sweep and XOR leg are off.
+MB/s); the CPU baseline, pair sweep and XOR leg are off. The legs run only
+under `--full`.
+* a plain run (no `--full`): the timed steps alone, and `--dump-outputs`
+  writes the last step's parity and rebuilt cells, compared with the oracle.
 """
 import json
 import os
@@ -20,7 +23,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "2", "--warmup", "1", "--chunk-mib", "0.5", "--cpu-baseline", "0", "--pairs", "0", "--xor", "0"]
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--chunk-mib", "0.5", "--cpu-baseline", "0", "--pairs", "0",
+         "--xor", "0"]
 
 
 def _bench(args, timeout):
@@ -117,6 +121,65 @@ def test_bench_two_ranks_over_the_rccl_transport(shape):
     _check_sharded(line["sharded"], 2, auto=False)
     assert line["sharded"]["transport"].startswith("RcclTransport"), line["sharded"]["transport"]
     assert line["sharded"]["shape"] == shape
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("chunk_kib,whole", [(64, True), (512, False)])
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(oracle, tmp_path, chunk_kib, whole):
+    """Without --full the line carries the headline figure and what the timed
+    steps' own events give, and none of the other legs; --steps sets the
+    number of timed steps. The dumped arrays are float32, within the size
+    limit, and equal the oracle's parity of the same seeded inputs (and the
+    inputs themselves for the rebuilt data cells): whole cells at 64 KiB, the
+    seeded sample at 512 KiB."""
+    import argparse
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    import redset_amd
+
+    out = tmp_path / "dump"
+    line = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--chunk-mib", str(chunk_kib / 1024),
+                   "--dump-outputs", str(out)], 100)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["full"] is False and line["ring_faults"] == 0 and line["hang_faults"] == 0
+    assert line["breakdown"]["encode_GBps"] > 0 and line["roofline"]["achieved"] > 0
+    for leg in ("sharded", "xor", "cpu_baseline", "rebuild_every_pair", "box_reference", "round_trip_bit_exact"):
+        assert leg not in line, leg
+
+    # the same inputs, made as the bench makes them, and the oracle's parity
+    p, e, lost, chunk = 11, 3, [1, 2], chunk_kib * 1024
+    d = p - e
+    pad = bench.cell_pad(argparse.Namespace(cell_pad_mib=-1.0), chunk)
+    lay = redset_amd.SetLayout.allocate(p, d, e, chunk, pad=pad)
+    bench.fill_set(lay, 1234)
+    lofi = [np.concatenate([lay.data_cell(r, s).cpu().numpy() for s in range(d)]) for r in range(p)]
+    torch.cuda.synchronize()
+    parity = [np.zeros(e * chunk, np.uint8) for _ in range(p)]
+    oracle.OracleRS(p, e).encode_set(lofi, parity, chunk)
+    want = {
+        "parity": [parity[r][i * chunk:(i + 1) * chunk] for r in range(p) for i in range(e)],
+        "rebuilt": [c for r in lost for c in
+                    [lofi[r][s * chunk:(s + 1) * chunk] for s in range(d)] +
+                    [parity[r][i * chunk:(i + 1) * chunk] for i in range(e)]],
+    }
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    total = 0
+    for name in ("parity", "rebuilt"):
+        got = np.load(out / f"{name}.npy")
+        total += got.nbytes
+        cells = want[name]
+        assert got.dtype == np.float32 and got.shape[0] == len(cells)
+        assert (got.shape[1] == chunk) is whole
+        for k, c in enumerate(cells):
+            ref = c if whole else c[rng.integers(0, chunk, got.shape[1])]
+            assert np.array_equal(got[k], ref.astype(np.float32)), (name, k)
+    assert sorted(f.name for f in out.iterdir()) == ["parity.npy", "rebuilt.npy"]
+    assert total <= 64 * 10**6
 
 
 @pytest.mark.timeout(300)

@@ -18,7 +18,7 @@ for r in $(seq "$rounds"); do
       twin) lib=$PWD/redset_amd/lib_test/libredset_hip.so ;;
       *) lib=$PWD/ab/lib_$b.so ;;
     esac
-    out=$(env ${lib:+REDSET_HIP_LIBRARY=$lib} "${envs[@]}" timeout -k 10 300 python bench.py --cpu-baseline 0 --pairs 0 \
+    out=$(env ${lib:+REDSET_HIP_LIBRARY=$lib} "${envs[@]}" timeout -k 10 300 python bench.py --full --cpu-baseline 0 --pairs 0 \
           $args 2>/dev/null | tail -1)
     s=$?
     [ $s -eq 0 ] || { echo "$b: bench exit $s"; exit $s; }

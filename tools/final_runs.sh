@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${1:-final}; mkdir -p "$OUT"; rm -f "$OUT/final_runs.jsonl"
 for i in $(seq 1 ${2:-5}); do
-  timeout -k 10 300 python bench.py > "$OUT/b.tmp" 2> "$OUT/b.err" || exit $?
+  timeout -k 10 300 python bench.py --full > "$OUT/b.tmp" 2> "$OUT/b.err" || exit $?
   tail -1 "$OUT/b.tmp" >> "$OUT/final_runs.jsonl"
 done
 python3 - "$OUT/final_runs.jsonl" <<'PY'

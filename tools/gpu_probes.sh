@@ -42,7 +42,7 @@ for probe in "$@"; do
         --master-port 29542 tools/gloo_p2p_probe.py --device cuda --reps 1 ;;
     n2)
       run n2_gloo 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29543 bench.py --gpus 2 --dist-backend gloo --chunk-mib 2 --steps 3 --warmup 1 \
+        --master-port 29543 bench.py --full --gpus 2 --dist-backend gloo --chunk-mib 2 --steps 3 --warmup 1 \
         --cpu-baseline 0 --pairs 0 ;;
     rank)
       for ex in ${RANK_EXCHANGES:-host sharded-mpi sharded-host}; do
@@ -84,7 +84,7 @@ for probe in "$@"; do
       for n in ${STUB_NS:-3 4}; do
         REDSET_HIP_LIBRARY=$PWD/redset_amd/lib_test/libredset_hip.so \
           REDSET_HIP_TEST_RCCL_LIBRARY=$PWD/tests/rcclstub/lib/librccl.so.1 \
-          run bench_stub_n$n 500 python bench.py --gpus $n --dist-backend gloo --sharded-transport rccl \
+          run bench_stub_n$n 500 python bench.py --full --gpus $n --dist-backend gloo --sharded-transport rccl \
             --chunk-mib 4 --steps 3 --warmup 1 --cpu-baseline 1 --cpu-seconds 1 --pairs 0 --xor 0 \
             --sharded-timeout 300
       done ;;
@@ -96,10 +96,10 @@ for probe in "$@"; do
       # against the gather shape's gf_mac plans (two ranks sharing one GPU)
       REDSET_HIP_LIBRARY=$PWD/redset_amd/lib_test/libredset_hip.so \
         REDSET_HIP_TEST_RCCL_LIBRARY=$PWD/tests/rcclstub/lib/librccl.so.1 \
-        run bench_stub_full_n2 900 python bench.py --gpus 2 --dist-backend gloo --sharded-transport rccl \
+        run bench_stub_full_n2 900 python bench.py --full --gpus 2 --dist-backend gloo --sharded-transport rccl \
           --steps 3 --warmup 1 --cpu-baseline 0 --pairs 0 --xor 0 --sharded-timeout 800 ;;
     wide)
-      W="--ranks 20 --encoding 4 --lost 1,2,3,4 --cpu-baseline 0 --pairs 0 --xor 0"
+      W="--full --ranks 20 --encoding 4 --lost 1,2,3,4 --cpu-baseline 0 --pairs 0 --xor 0"
       run wide_bench 300 python bench.py --steps 10 --warmup 3 $W
       run wide_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/wide_prof" -o wide -- \
         python3 bench.py --steps 10 --warmup 3 $W

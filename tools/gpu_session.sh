@@ -21,27 +21,27 @@ s=$?; echo "smoke exit $s" | tee -a "$OUT/progress.txt"; tail -2 "$OUT/smoke.log
 ok $s || exit $s
 
 echo "== bench" | tee -a "$OUT/progress.txt"
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
 s=$?; echo "bench exit $s" | tee -a "$OUT/progress.txt"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 ok $s || exit $s
 
 echo "== rocprofv3 kernel stats" | tee -a "$OUT/progress.txt"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- \
-  python3 bench.py --steps 20 --warmup 3 --cpu-baseline 0 --pairs 0 > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+  python3 bench.py --full --steps 20 --warmup 3 --cpu-baseline 0 --pairs 0 > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
 s=$?; echo "rocprof exit $s" | tee -a "$OUT/progress.txt"
 ok $s || exit $s
 echo "== rocprofv3 PMC FETCH_SIZE / WRITE_SIZE (separate passes)" | tee -a "$OUT/progress.txt"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- \
-  python3 bench.py --steps 4 --warmup 1 --cpu-baseline 0 --pairs 0 > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
+  python3 bench.py --full --steps 4 --warmup 1 --cpu-baseline 0 --pairs 0 > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
 s=$?; echo "pmc fetch exit $s" | tee -a "$OUT/progress.txt"; ok $s || exit $s
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o write -- \
-  python3 bench.py --steps 4 --warmup 1 --cpu-baseline 0 --pairs 0 > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
+  python3 bench.py --full --steps 4 --warmup 1 --cpu-baseline 0 --pairs 0 > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
 s=$?; echo "pmc write exit $s" | tee -a "$OUT/progress.txt"; ok $s || exit $s
 python3 tools/pmc_traffic.py "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/traffic.json" > /dev/null
 echo "== done" | tee -a "$OUT/progress.txt"
 echo "== N=2 gloo rehearsal of bench.py --gpus 2 (both ranks on the one GPU)" | tee -a "$OUT/progress.txt"
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 2 --dist-backend gloo --chunk-mib 2 --steps 3 --warmup 1 \
+  --master-port 29533 bench.py --full --gpus 2 --dist-backend gloo --chunk-mib 2 --steps 3 --warmup 1 \
   --cpu-baseline 0 --pairs 0 > "$OUT/n2_gloo.json" 2> "$OUT/n2_gloo.err"
 s=$?; echo "n2 gloo exit $s" | tee -a "$OUT/progress.txt"; ok $s || exit $s
 echo "== done (gloo)" | tee -a "$OUT/progress.txt"
