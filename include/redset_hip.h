@@ -47,7 +47,9 @@ enum {
   REDSET_HIP_PLAN_RS_ENCODE = 1,
   REDSET_HIP_PLAN_RS_REBUILD = 2,
   REDSET_HIP_PLAN_XOR_ENCODE = 3,
-  REDSET_HIP_PLAN_XOR_REBUILD = 4
+  REDSET_HIP_PLAN_XOR_REBUILD = 4,
+  REDSET_HIP_PLAN_RS_VERIFY = 5,
+  REDSET_HIP_PLAN_XOR_VERIFY = 6
 };
 
 typedef struct {
@@ -127,6 +129,67 @@ int redset_hip_xor_plan_rebuild(int ranks, int root, unsigned char* const* lofi,
 int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream);
 int redset_hip_plan_get_info(const redset_hip_plan* plan, redset_hip_plan_info* info);
 void redset_hip_plan_destroy(redset_hip_plan* plan);
+
+/* ---- set verification (scrub) ---------------------------------------- */
+/*
+ * Does the stored parity still match the stored data, and if not, where and
+ * in which member? A verify plan reads every cell of the set once, writes no
+ * cell, and leaves one report row per (stripe, parity row): how many bytes of
+ * that stored parity cell differ from the parity of the stored data (the
+ * syndrome's nonzero bytes) and the first such byte. A damaged DATA cell
+ * shows in all e rows of its stripe, a damaged PARITY cell in its own row
+ * only; with e >= 2 that names the damaged member (locate, below), which
+ * redset_hip_rs_plan_rebuild then repairs. The reference has no counterpart:
+ * it finds a damaged file only when a restart reads it.
+ */
+typedef struct {
+  unsigned long long mismatch_bytes;  /* bytes of this parity row that differ from the data's parity */
+  unsigned long long first_offset;    /* smallest differing byte offset in the cell; ~0ULL if none */
+} redset_hip_verify_row;              /* row [stripe * e + i]: stripe's parity row i (e = 1 for XOR) */
+
+/* Verify plans execute through redset_hip_plan_execute like any plan: kernel
+ * launches only (the report is reset by one), no allocation and no
+ * host synchronisation (safe inside hipStreamBeginCapture); every execute
+ * first resets the report on the stream, so a replay starts clean. No cell is
+ * modified. Stripes of d = p - e <= 16 data cells and e <= 4 (XOR: p <= 16)
+ * run FUSED: one pass reads each cell once and writes nothing
+ * (plan info: bytes_written == 0, bytes_read == p*(d+e)*chunk_size for RS,
+ * p*p*chunk_size for XOR). Wider shapes -- any valid (p, e) works -- compute
+ * the parity of <= 4 rows at a time into plan-owned scratch with the
+ * combine passes, in column windows of <= 8 MiB, and check the scratch
+ * against the stored cells: the scratch is bounded by 4 x 8 MiB = 32 MiB
+ * whatever the set, and counts in bytes_written. An XOR row's report names
+ * the stripe, not a cell: one parity row cannot tell which cell is wrong. */
+int redset_hip_rs_plan_verify(const redset_hip_rs* rs, unsigned char* const* lofi,
+                              unsigned char* const* parity, size_t chunk_size, size_t cell_stride,
+                              redset_hip_plan** out);
+int redset_hip_xor_plan_verify(int ranks, unsigned char* const* lofi, unsigned char* const* xorc,
+                               size_t chunk_size, size_t cell_stride, redset_hip_plan** out);
+/* The report of the plan's last execute: p * e rows (nrows must be at least
+ * that; rows and total_mismatch_bytes may each be NULL). Ordered on `stream`
+ * after the work already there; waits for it. */
+int redset_hip_plan_verify_report(const redset_hip_plan* plan, void* stream, redset_hip_verify_row* rows,
+                                  int nrows, unsigned long long* total_mismatch_bytes);
+
+/* Locate (host): `syndrome` is e bytes of one byte column of stripe chunk_id
+ * (stored parity ^ parity of stored data, row by row). *member_out = the one
+ * member whose single wrong byte explains it, or -1 (clean, e < 2, or no
+ * single member explains it). Rule: exactly one nonzero row i names the
+ * holder of parity row i, member (chunk_id - i) mod p; otherwise the answer
+ * is the unique data member m for which one value x gives
+ * syndrome[j] = A[j][m] * x for every row j (A = the parity rows of the
+ * encoding matrix). Any two columns of [A | I] are independent -- the code
+ * rebuilds any e erasures -- so with e >= 2 a single wrong member is never
+ * mistaken for another; two wrong members in one column may look like a
+ * third when e == 2, as with any code of distance 3. */
+int redset_hip_rs_locate_syndrome(const redset_hip_rs* rs, int chunk_id, const unsigned char* syndrome,
+                                  int* member_out);
+/* After an execute of an RS verify plan: reads back the p bytes of `stripe`
+ * at its first differing offset (ordered on `stream`, waits) and locates.
+ * *offset_out = that offset (~0ULL and member -1 if the stripe is clean).
+ * XOR plans answer -1: one parity row locates nothing. */
+int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int stripe, int* member_out,
+                                  unsigned long long* offset_out);
 
 /* ---- stripe primitives (one stripe, device pointers) ----------------- */
 
@@ -219,6 +282,21 @@ int redset_hip_xor_encode_stream(int ranks, size_t chunk_size, int first_stripe,
 int redset_hip_xor_rebuild_stream(int ranks, int root, size_t chunk_size, int first_stripe, int nstripes,
                                   size_t slice_bytes, int io_threads, const redset_hip_io* io,
                                   redset_hip_stream_stats* stats);
+
+/* Verify a host-resident set (see "set verification" above): the same read ->
+ * H2D -> kernel pipeline with the check kernels, and no D2H or write stage:
+ * io->write is never called (it may be NULL), page-locked cells (io->map) are
+ * read in place. rows: (stripe - first_stripe) * e + i for the stripes of
+ * the call, nrows at least that many; offsets are cell offsets whatever the
+ * slice. Returns REDSET_SUCCESS when the check RAN (damage is in the rows,
+ * not in the return code), REDSET_FAILURE on I/O or device errors or when the
+ * hang count moved. Wide stripes use <= 32 MiB of device scratch. */
+int redset_hip_rs_verify_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                size_t slice_bytes, int io_threads, const redset_hip_io* io,
+                                redset_hip_stream_stats* stats, redset_hip_verify_row* rows, int nrows);
+int redset_hip_xor_verify_stream(int ranks, size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
+                                 int io_threads, const redset_hip_io* io, redset_hip_stream_stats* stats,
+                                 redset_hip_verify_row* rows, int nrows);
 
 /* The streaming calls keep a successful call's three streams and (up to
  * 256 MiB pinned, 1 GiB of device memory) its staging buffers for the next

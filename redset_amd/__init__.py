@@ -13,6 +13,7 @@ from .codec import (  # noqa: F401
     Plan,
     RSCodec,
     SetLayout,
+    VerifyPlan,
     gf_combine,
     cell_stride,
     ring_faults,
@@ -20,6 +21,9 @@ from .codec import (  # noqa: F401
     xor_combine,
     xor_plan_encode,
     xor_plan_rebuild,
+    xor_plan_verify,
 )
+from .setfiles import verify_set  # noqa: F401
+from .stream import rs_verify_stream, xor_verify_stream  # noqa: F401
 
 __version__ = "0.1.0"

@@ -23,6 +23,8 @@ PLAN_RS_ENCODE = 1
 PLAN_RS_REBUILD = 2
 PLAN_XOR_ENCODE = 3
 PLAN_XOR_REBUILD = 4
+PLAN_RS_VERIFY = 5
+PLAN_XOR_VERIFY = 6
 
 # every symbol include/redset_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -76,6 +78,13 @@ EXPORTED_SYMBOLS = (
     "redset_hip_xor_sharded_plan_ex",
     "redset_hip_sharded_get_shape",
     "redset_hip_abi_version",
+    "redset_hip_rs_plan_verify",
+    "redset_hip_xor_plan_verify",
+    "redset_hip_plan_verify_report",
+    "redset_hip_rs_locate_syndrome",
+    "redset_hip_plan_verify_locate",
+    "redset_hip_rs_verify_stream",
+    "redset_hip_xor_verify_stream",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -114,6 +123,12 @@ class PlanInfo(ctypes.Structure):
         ("bytes_read", c_ulonglong),
         ("bytes_written", c_ulonglong),
     ]
+
+
+class VerifyRow(ctypes.Structure):
+    """redset_hip_verify_row: one (stripe, parity row) of a verify report."""
+
+    _fields_ = [("mismatch_bytes", c_ulonglong), ("first_offset", c_ulonglong)]
 
 
 class StreamIO(ctypes.Structure):
@@ -302,6 +317,15 @@ _SIGNATURES = {
                 POINTER(c_void_p)]),
     "redset_hip_sharded_get_shape": (c_int, [c_void_p, POINTER(ShapeInfo), c_size_t]),
     "redset_hip_abi_version": (c_int, []),
+    "redset_hip_rs_plan_verify": (c_int, [c_void_p, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
+    "redset_hip_xor_plan_verify": (c_int, [c_int, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
+    "redset_hip_plan_verify_report": (c_int, [c_void_p, c_void_p, POINTER(VerifyRow), c_int, POINTER(c_ulonglong)]),
+    "redset_hip_rs_locate_syndrome": (c_int, [c_void_p, c_int, POINTER(c_ubyte), POINTER(c_int)]),
+    "redset_hip_plan_verify_locate": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_ulonglong)]),
+    "redset_hip_rs_verify_stream": (
+        c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, _STP, POINTER(VerifyRow), c_int]),
+    "redset_hip_xor_verify_stream": (
+        c_int, [c_int, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, _STP, POINTER(VerifyRow), c_int]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

@@ -79,6 +79,56 @@ class Plan:
             pass
 
 
+NO_OFFSET = (1 << 64) - 1  # first_offset of a report row where nothing differs
+
+
+def rows_to_arrays(rows, stripes: int, e: int):
+    """(mismatch[stripes, e], first[stripes, e]) of a redset_hip_verify_row array."""
+    mism = np.array([int(r.mismatch_bytes) for r in rows], dtype=np.uint64).reshape(stripes, e)
+    first = np.array([int(r.first_offset) for r in rows], dtype=np.uint64).reshape(stripes, e)
+    return mism, first
+
+
+class VerifyPlan(Plan):
+    """A verify (scrub) plan: execute() reads every cell of the set once and
+    writes none; report() says which stored parity rows no longer match the
+    stored data (include/redset_hip.h, "set verification")."""
+
+    def report(self, stream=None):
+        """``(mismatch, first)``: numpy uint64 arrays [p, e] -- differing bytes
+        of stripe c's parity row i and the first differing cell offset
+        (NO_OFFSET where nothing differs) -- of the last execute. Waits for
+        the work on ``stream``."""
+        p, e = int(self.info.ranks), int(self.info.encoding)
+        rows = (_lib.VerifyRow * (p * e))()
+        _lib.check(_lib.load().redset_hip_plan_verify_report(self._h, _stream_handle(stream), rows, p * e, None),
+                   "plan_verify_report")
+        return rows_to_arrays(rows, p, e)
+
+    @property
+    def clean(self) -> bool:
+        """No byte of the last execute's report differs."""
+        from ctypes import c_ulonglong
+
+        total = c_ulonglong(0)
+        _lib.check(_lib.load().redset_hip_plan_verify_report(self._h, _stream_handle(None), None, 0,
+                                                             ctypes.byref(total)), "plan_verify_report")
+        return total.value == 0
+
+    def locate(self, stripe: int, stream=None):
+        """``(member, offset)`` for ``stripe`` after an execute: the member
+        whose single wrong byte explains the stripe's first differing column
+        (-1: clean, or no single member explains it, or an XOR set) and that
+        column's cell offset (None if the stripe is clean)."""
+        from ctypes import c_ulonglong
+
+        m, off = c_int(-1), c_ulonglong(0)
+        _lib.check(_lib.load().redset_hip_plan_verify_locate(self._h, _stream_handle(stream), stripe,
+                                                             ctypes.byref(m), ctypes.byref(off)),
+                   "plan_verify_locate")
+        return int(m.value), (None if off.value == NO_OFFSET else int(off.value))
+
+
 class RSCodec:
     """GF(2^8) tables + encoding matrix for a set of ``ranks`` members with
     ``encoding`` parity cells per stripe (redset_construct_rs,
@@ -142,6 +192,27 @@ class RSCodec:
         )
         return Plan(h, (self, lofi, parity))
 
+    def plan_verify(self, lofi, parity, chunk_size: int, cell_stride: Optional[int] = None) -> "VerifyPlan":
+        """Check every stripe's stored parity against its stored data."""
+        stride = chunk_size if cell_stride is None else cell_stride
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_verify(self._h, a, b, chunk_size, stride, ctypes.byref(h)),
+            "rs_plan_verify",
+        )
+        return VerifyPlan(h, (self, lofi, parity))
+
+    def locate_syndrome(self, chunk_id: int, syndrome) -> int:
+        """The member whose single wrong byte gives this syndrome column (e
+        bytes: stored parity ^ parity of stored data) in stripe chunk_id, or
+        -1 (include/redset_hip.h redset_hip_rs_locate_syndrome)."""
+        syn = (c_ubyte * self.encoding)(*[int(x) for x in syndrome])
+        m = c_int(-1)
+        _lib.check(_lib.load().redset_hip_rs_locate_syndrome(self._h, chunk_id, syn, ctypes.byref(m)),
+                   "rs_locate_syndrome")
+        return int(m.value)
+
     def close(self) -> None:
         if self._h:
             _lib.load().redset_hip_rs_destroy(self._h)
@@ -175,6 +246,18 @@ def xor_plan_rebuild(ranks: int, root: int, lofi, xorc, chunk_size: int,
         "xor_plan_rebuild",
     )
     return Plan(h, (lofi, xorc))
+
+
+def xor_plan_verify(ranks: int, lofi, xorc, chunk_size: int, cell_stride: Optional[int] = None) -> VerifyPlan:
+    """Check that the XOR of every stripe's p cells is zero."""
+    stride = chunk_size if cell_stride is None else cell_stride
+    a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in xorc])
+    h = c_void_p()
+    _lib.check(
+        _lib.load().redset_hip_xor_plan_verify(ranks, a, b, chunk_size, stride, ctypes.byref(h)),
+        "xor_plan_verify",
+    )
+    return VerifyPlan(h, (lofi, xorc))
 
 
 def gf_combine(inputs, outputs, coeffs: np.ndarray, nbytes: int, accumulate: bool = False, stream=None) -> None:

@@ -201,6 +201,124 @@ struct XorAcc {
   }
 };
 
+// Check sinks (set verification): the same incremental combine as GfAcc /
+// XorAcc, but finish(v) compares with what is stored and stores nothing.
+// Fast path: the syndrome of the position is zero -- an OR over what was
+// loaded and computed, no atomics. Slow path: the lane counts the differing
+// bytes of each output row and sends its first (smallest) differing byte
+// offset to the report (atomicMin, once per lane and row); flush() adds the
+// lane's counts to the launch's report rows after the sweep
+// (codec_kernels.h GfCheckLaunch::report: `report_rows` mismatch words, then
+// `report_rows` first-offset words), the only thing a check kernel writes.
+// bit 7 of every nonzero byte of x
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t x) {
+  return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+}
+// One row's tally of a lane. A lane meets its positions in ascending order
+// (the sweep's vectors, then the byte path), so the first difference it
+// notes is its smallest: that one goes to the report's first-offset word at
+// once (atomicMin), later ones only count. `where`: the report words of the
+// row and the cell offset of the launch's first byte (wave-uniform).
+struct CheckWhere {
+  unsigned long long* count;
+  unsigned long long* first;
+  unsigned long long base;
+};
+struct CheckTally {
+  unsigned cnt;
+  __device__ __forceinline__ void reset() { cnt = 0; }
+  __device__ __forceinline__ void note(const CheckWhere& w, unsigned long long off, unsigned n) {
+    if (cnt == 0) atomicMin(w.first, w.base + off);
+    cnt += n;
+  }
+  // a nonzero difference vector of position v
+  __device__ __forceinline__ void note_vec(const CheckWhere& w, size_t v, const v4u& r) {
+    const uint32_t t[4] = {nonzero_bytes(r.x), nonzero_bytes(r.y), nonzero_bytes(r.z), nonzero_bytes(r.w)};
+    unsigned n = 0;
+    int fb = -1;
+#pragma unroll
+    for (int q = 3; q >= 0; --q) {
+      n += __builtin_popcount(t[q]);
+      if (t[q]) fb = q * 4 + (__builtin_ctz(t[q]) >> 3);
+    }
+    note(w, static_cast<unsigned long long>(v) * 16u + static_cast<unsigned>(fb), n);
+  }
+  __device__ __forceinline__ void flush(const CheckWhere& w) {
+    if (cnt != 0) atomicAdd(w.count, static_cast<unsigned long long>(cnt));
+  }
+};
+
+// GfAcc<NOUT, true> with the stored parity cells read, never written:
+// r = computed ^ stored is the syndrome of the position
+template <int NOUT>
+struct GfCheck {
+  const uint32_t* lds;
+  g_cu4* out[NOUT];
+  uint32_t acc[16];
+  CheckTally tally[NOUT];
+  CheckWhere where;  // of row 0; row j is j words on
+  __device__ __forceinline__ CheckWhere row(int j) const { return CheckWhere{where.count + j, where.first + j, where.base}; }
+  __device__ __forceinline__ void reset(unsigned long long* report, int report_rows, int r, size_t base) {
+    where = CheckWhere{report + r, report + report_rows + r, base};
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) tally[j].reset();
+  }
+  __device__ __forceinline__ void begin() {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) acc[b] = 0;
+  }
+  template <int I0, int N, int TB = 0>
+  __device__ __forceinline__ void add(const v4u (&x)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) gf_acc_input<TB>(lds, x[i], I0 + i, acc);
+  }
+  __device__ __forceinline__ void finish(size_t v) {
+    v4u r[NOUT];
+    // each stored byte is read once: non-temporal, as the ring's own loads
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) r[j] = __builtin_nontemporal_load(out[j] + v);
+    uint32_t any = 0;
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) {
+      r[j].x ^= gather_byte(acc[0], acc[1], acc[2], acc[3], j);
+      r[j].y ^= gather_byte(acc[4], acc[5], acc[6], acc[7], j);
+      r[j].z ^= gather_byte(acc[8], acc[9], acc[10], acc[11], j);
+      r[j].w ^= gather_byte(acc[12], acc[13], acc[14], acc[15], j);
+      any |= r[j].x | r[j].y | r[j].z | r[j].w;
+    }
+    if (any == 0) return;
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j)
+      if ((r[j].x | r[j].y | r[j].z | r[j].w) != 0) tally[j].note_vec(row(j), v, r[j]);
+  }
+  __device__ __forceinline__ void flush() {
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) tally[j].flush(row(j));
+  }
+};
+
+// XOR scheme: every cell of the stripe, the parity cell included, comes
+// through the ring as an input; their XOR must be zero
+struct XorCheck {
+  v4u r;
+  CheckTally tally;
+  CheckWhere where;
+  __device__ __forceinline__ void reset(unsigned long long* report, int report_rows, int row, size_t base) {
+    where = CheckWhere{report + row, report + report_rows + row, base};
+    tally.reset();
+  }
+  __device__ __forceinline__ void begin() { r = v4u{0, 0, 0, 0}; }
+  template <int I0, int N>
+  __device__ __forceinline__ void add(const v4u (&x)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) r ^= x[i];
+  }
+  __device__ __forceinline__ void finish(size_t v) {
+    if ((r.x | r.y | r.z | r.w) != 0) tally.note_vec(where, v, r);
+  }
+  __device__ __forceinline__ void flush() { tally.flush(where); }
+};
+
 // Loader-wave LDS-DMA ring (shape per kernel below: D items in flight, R
 // rows per item). Wave 0 of the block is the loader: it streams items -- R
 // 1 KiB rows (64 lanes x 16 B) of every input -- with global_load_lds_dwordx4 into a
@@ -1454,6 +1572,78 @@ __device__ __forceinline__ void xor_body(const XorLaunch& L, const XorJob& J, in
   }
 }
 
+// Set verification: gf_mac_body / xor_body with the check sinks. One job =
+// one stripe (or one group of a wide stripe's parity rows against scratch):
+// its syndrome counts go to report rows [row, row + NOUT). Per-job body only
+// (side by side, or every block sweeping the jobs in turn): no wait without
+// a fallback, so nothing here can count in the hang word.
+template <int NIN, int NOUT>
+__device__ __forceinline__ void gf_check_body(const GfCheckLaunch& C, const GfJob& J, int part, int row) {
+  const GfLaunch& L = C.g;
+  v4u* const smem = gf_lds<NIN>();
+  uint32_t* const lds = reinterpret_cast<uint32_t*>(smem);
+
+  build_tables(lds, J, NIN, NOUT);
+  __syncthreads();
+
+  GfCheck<NOUT> body;
+  body.lds = lds;
+  body.reset(C.report, C.report_rows, row, C.base);
+#pragma unroll
+  for (int j = 0; j < NOUT; ++j) body.out[j] = (g_cu4*) (J.out[j]);
+  const size_t nvec = L.bytes_only ? 0 : L.nbytes / 16;
+  const size_t vstep = static_cast<size_t>(L.blocks_per_job) * kBlock;
+  if (nvec > 0) {
+    g_cu4* in[NIN];
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) in[i] = (g_cu4*) (J.in[i]);
+    constexpr int kDepth = ring_depth<NIN, kRingGfRows, kRingRowsInFlight>();
+    ring_sweep<NIN, kRingGfRows, kDepth>(smem + kTableVecs, in, nvec, static_cast<size_t>(L.blocks_per_job),
+                                         static_cast<size_t>(part), L.fault, RING_SPIN_CAP(L), body);
+  }
+  // byte path, as gf_mac_body's: the tail, or every byte of unaligned cells
+  const size_t tail0 = nvec * 16;
+  for (size_t k = tail0 + static_cast<size_t>(part) * kBlock + threadIdx.x; k < L.nbytes; k += vstep) {
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) {
+      const uint32_t b = J.in[i][k];
+      acc ^= lds_at(lds, i * kTableBytes + (b & 15u) * 4) ^ lds_at(lds, i * kTableBytes + kHiBase + (b >> 4) * kHiStride);
+    }
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j)
+      if (static_cast<uint8_t>(acc >> (8 * j)) != J.out[j][k]) body.tally[j].note(body.row(j), k, 1u);
+  }
+  body.flush();
+}
+
+template <int NIN>
+__device__ __forceinline__ void xor_check_body(const XorCheckLaunch& C, const XorJob& J, int part, int row) {
+  const XorLaunch& L = C.x;
+  XorCheck body;
+  body.reset(C.report, C.report_rows, row, C.base);
+  const size_t nvec = L.bytes_only ? 0 : L.nbytes / 16;
+  const size_t vstep = static_cast<size_t>(L.blocks_per_job) * kBlock;
+  if (nvec > 0) {
+    g_cu4* in[NIN];
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) in[i] = (g_cu4*) (J.in[i]);
+    constexpr int kRows = NIN > kRingXorWide ? 1 : kRingXorRows;
+    constexpr int kDepth = ring_depth<NIN, kRows, kRows == 1 ? kRingXorRowsInFlight : kRingRowsInFlight>();
+    v4u* const ring = xor_lds<NIN, kRows>();
+    ring_sweep<NIN, kRows, kDepth>(ring, in, nvec, static_cast<size_t>(L.blocks_per_job), static_cast<size_t>(part),
+                                   L.fault, RING_SPIN_CAP(L), body);
+  }
+  const size_t tail0 = nvec * 16;
+  for (size_t k = tail0 + static_cast<size_t>(part) * kBlock + threadIdx.x; k < L.nbytes; k += vstep) {
+    uint8_t r = 0;
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) r ^= J.in[i][k];
+    if (r) body.tally.note(body.where, k, 1u);
+  }
+  body.flush();
+}
+
 // entry points: jobs from a device array (plans), or one job passed by
 // value in the kernel arguments (stripe primitives, no device descriptor)
 template <int NIN, int NOUT, bool ACC>
@@ -1511,6 +1701,44 @@ REDSET_KERNEL xor_kernel_arg(XorLaunch L, XorJob J) {
   xor_body<NIN, ACC>(L, J, blockIdx.x);
 }
 
+// check entry points: the jobs of a device array (C.g.jobs / C.x.jobs), or,
+// when that is null, the one job passed by value
+template <int NIN, int NOUT>
+REDSET_KERNEL gf_check_kernel(GfCheckLaunch C, GfJob J1) {
+  const GfLaunch& L = C.g;
+  if (!L.jobs) {
+    gf_check_body<NIN, NOUT>(C, J1, blockIdx.x, C.row0);
+    return;
+  }
+  if (L.sequential == kJobsInKernel) {
+    for (int j = 0; j < L.njobs; ++j) {
+      if (j > 0) __syncthreads();  // all waves are done with the last job's tables
+      gf_check_body<NIN, NOUT>(C, L.jobs[L.job0 + j], blockIdx.x, C.row0 + (L.job0 + j) * C.row_stride);
+    }
+    return;
+  }
+  const int job = blockIdx.x / L.blocks_per_job;
+  gf_check_body<NIN, NOUT>(C, L.jobs[L.job0 + job], blockIdx.x - job * L.blocks_per_job,
+                           C.row0 + (L.job0 + job) * C.row_stride);
+}
+
+template <int NIN>
+REDSET_KERNEL xor_check_kernel(XorCheckLaunch C, XorJob J1) {
+  const XorLaunch& L = C.x;
+  if (!L.jobs) {
+    xor_check_body<NIN>(C, J1, blockIdx.x, C.row0);
+    return;
+  }
+  if (L.sequential == kJobsInKernel) {
+    for (int j = 0; j < L.njobs; ++j)
+      xor_check_body<NIN>(C, L.jobs[L.job0 + j], blockIdx.x, C.row0 + (L.job0 + j) * C.row_stride);
+    return;
+  }
+  const int job = blockIdx.x / L.blocks_per_job;
+  xor_check_body<NIN>(C, L.jobs[L.job0 + job], blockIdx.x - job * L.blocks_per_job,
+                      C.row0 + (L.job0 + job) * C.row_stride);
+}
+
 template <int N>
 constexpr KernelSet make_kernel_set() {
   return KernelSet{
@@ -1524,6 +1752,8 @@ constexpr KernelSet make_kernel_set() {
        {&gf_mac_kernel_arg<N, 4, false>, &gf_mac_kernel_arg<N, 4, true>}},
       {&xor_kernel<N, false>, &xor_kernel<N, true>},
       {&xor_kernel_arg<N, false>, &xor_kernel_arg<N, true>},
+      {&gf_check_kernel<N, 1>, &gf_check_kernel<N, 2>, &gf_check_kernel<N, 3>, &gf_check_kernel<N, 4>},
+      &xor_check_kernel<N>,
   };
 }
 

@@ -101,12 +101,44 @@ struct XorLaunch {
   unsigned table_delay;     // (see GfLaunch)
 };
 
+// Set verification (codec_device.h gf_check_kernel / xor_check_kernel): a
+// launch of the GF or XOR shape whose kernels compare instead of storing. GF
+// jobs: in[] = the stripe's data cells, out[] = the STORED parity cells (only
+// read), coef as the encode's. XOR jobs: in[] = every cell of the stripe, the
+// parity cell included (out unused); their XOR must be zero. Only the job
+// orders 0, kJobsInLaunches and kJobsInKernel. Job k of the launch reports to
+// rows [row0 + k * row_stride, + nout) of `report`: report[row] counts the
+// differing bytes, report[report_rows + row] holds the smallest differing
+// byte offset (`base` + offset in the launch's cells; ~0 if none).
+struct GfCheckLaunch {
+  GfLaunch g;
+  unsigned long long* report;  // device: report_rows counts, then report_rows offsets
+  int report_rows;
+  int row0, row_stride;
+  int reset;                   // the launcher resets the launch's rows on its stream first
+  size_t base;                 // cell offset of the launch's first byte (slices, windows)
+};
+struct XorCheckLaunch {
+  XorLaunch x;
+  unsigned long long* report;
+  int report_rows;
+  int row0, row_stride;
+  int reset;
+  size_t base;
+};
+
 // launchers (codec_kernels.hip); return hipError_t as int
 int launch_gf(const GfLaunch& L, void* stream);
 int launch_xor(const XorLaunch& L, void* stream);
 // one job passed by value (L.jobs / L.njobs ignored; grid = blocks_per_job)
 int launch_gf_single(const GfLaunch& L, const GfJob& J, void* stream);
 int launch_xor_single(const XorLaunch& L, const XorJob& J, void* stream);
+// check launches: the jobs of C.g.jobs / C.x.jobs, or `single` (by value,
+// one job over blocks_per_job blocks) when that is null
+int launch_gf_check(const GfCheckLaunch& C, const GfJob* single, void* stream);
+int launch_xor_check(const XorCheckLaunch& C, const XorJob* single, void* stream);
+// rows [row0, row0 + nrows) of a report back to "nothing differs", on `stream`
+int reset_report(unsigned long long* report, int report_rows, int row0, int nrows, void* stream);
 // device properties used to size grids
 int device_cu_count();
 // the current device's count of capped loader-ring spins since the last
@@ -137,11 +169,15 @@ using GfKernel = void (*)(GfLaunch);
 using XorKernel = void (*)(XorLaunch);
 using GfKernelArg = void (*)(GfLaunch, GfJob);
 using XorKernelArg = void (*)(XorLaunch, XorJob);
+using GfCheckKernel = void (*)(GfCheckLaunch, GfJob);
+using XorCheckKernel = void (*)(XorCheckLaunch, XorJob);
 struct KernelSet {
   GfKernel gf[kMaxOut][2];
   GfKernelArg gf_arg[kMaxOut][2];
   XorKernel xr[2];
   XorKernelArg xr_arg[2];
+  GfCheckKernel gf_check[kMaxOut];  // [nout - 1]
+  XorCheckKernel xr_check;
 };
 
 }  // namespace redset_hip

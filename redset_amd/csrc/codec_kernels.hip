@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 
 #include "codec_kernels.h"
 
@@ -243,6 +244,75 @@ int launch_xor(const XorLaunch& L, void* stream) {
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// Rows [row0, row0 + nrows) of a report back to "nothing differs": counts 0,
+// first offsets ~0. A kernel, not two memsets: a memset node of a captured
+// graph replayed a stale fill pattern into the rows on its second replay
+// (tests/test_gpu_verify.py::test_damage), plain stores replay as written.
+__global__ void report_reset_kernel(unsigned long long* report, int report_rows, int row0, int nrows) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nrows) {
+    report[row0 + i] = 0ull;
+    report[report_rows + row0 + i] = ~0ull;
+  }
+}
+
+int reset_report(unsigned long long* report, int report_rows, int row0, int nrows, void* stream) {
+  if (!report || nrows <= 0) return hipSuccess;
+  if (row0 < 0 || row0 + nrows > report_rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(report_reset_kernel, dim3(static_cast<unsigned>((nrows + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), report, report_rows, row0, nrows);
+  return hipGetLastError();
+}
+
+namespace {
+// the launches of a check: as launch_gf / launch_xor for the orders 0,
+// kJobsInLaunches and kJobsInKernel (any other order runs as kJobsInKernel)
+template <class Check, class Launch, class Job, class Kernel>
+int launch_check(const Check& C, const Launch& L, Launch Check::*member, const Job* single, int nout, Kernel k,
+                 void* stream) {
+  const int njobs = single ? 1 : L.njobs;
+  if (C.reset) {
+    // every replay starts clean, whatever an earlier launch left (the
+    // treatment the claim counters get)
+    const int rows = single ? nout : (njobs - 1) * C.row_stride + nout;
+    if (int e = reset_report(C.report, C.report_rows, C.row0, rows, stream)) return e;
+  }
+  if (njobs == 0 || L.nbytes == 0) return hipSuccess;
+  Job none;
+  std::memset(&none, 0, sizeof(none));
+  const bool in_kernel = !single && L.sequential != 0 && L.sequential != kJobsInLaunches;
+  const int per = single ? 1 : L.sequential == kJobsInLaunches ? std::max(1, L.group) : njobs;
+  for (int j = 0; j < njobs; j += per) {
+    Check one = C;
+    Launch& o = one.*member;
+    o.job0 = j;
+    o.sequential = in_kernel ? kJobsInKernel : 0;
+    if (single) o.jobs = nullptr;
+    set_launch_knobs(o);
+    const int n = in_kernel ? 1 : std::min(per, njobs - j);
+    const dim3 grid(static_cast<unsigned>(n * L.blocks_per_job));
+    hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), one, single ? *single : none);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+}  // namespace
+
+int launch_gf_check(const GfCheckLaunch& C, const GfJob* single, void* stream) {
+  const GfLaunch& L = C.g;
+  if (L.nin < 1 || L.nin > kMaxIn || L.nout < 1 || L.nout > kMaxOut || !C.report) return hipErrorInvalidValue;
+  if (!single && !L.jobs && L.njobs > 0) return hipErrorInvalidValue;
+  return launch_check(C, L, &GfCheckLaunch::g, single, L.nout, kernel_set(L.nin).gf_check[L.nout - 1], stream);
+}
+
+int launch_xor_check(const XorCheckLaunch& C, const XorJob* single, void* stream) {
+  const XorLaunch& L = C.x;
+  if (L.nin < 1 || L.nin > kMaxIn || !C.report) return hipErrorInvalidValue;
+  if (!single && !L.jobs && L.njobs > 0) return hipErrorInvalidValue;
+  return launch_check(C, L, &XorCheckLaunch::x, single, 1, kernel_set(L.nin).xr_check, stream);
 }
 
 }  // namespace redset_hip

@@ -25,11 +25,13 @@
 
 using redset_hip::CellRef;
 using redset_hip::fail;
+using redset_hip::GfCheckLaunch;
 using redset_hip::GfJob;
 using redset_hip::GfLaunch;
 using redset_hip::kMaxIn;
 using redset_hip::kMaxOut;
 using redset_hip::StripeMap;
+using redset_hip::XorCheckLaunch;
 using redset_hip::XorJob;
 using redset_hip::XorLaunch;
 
@@ -43,6 +45,22 @@ struct redset_hip_plan {
   unsigned* d_claim = nullptr;  // kJobsClaimed launches' queue counters
   std::vector<GfLaunch> gf_launches;
   std::vector<XorLaunch> xor_launches;
+  // verify plans (REDSET_HIP_PLAN_*_VERIFY): fused check launches over the
+  // device job arrays above, or wide stripes run one after another through
+  // the scratch; the report all of them add to; what locate needs
+  std::vector<redset_hip::GfCheckLaunch> gf_checks;
+  std::vector<redset_hip::XorCheckLaunch> xor_checks;
+  struct WideStripe {
+    StripeMap map;
+    std::vector<const uint8_t*> in, stored;
+    int row0;
+  };
+  std::vector<WideStripe> wide;
+  unsigned long long* d_report = nullptr;  // report_rows counts, then report_rows first offsets
+  int report_rows = 0;
+  uint8_t* d_scratch = nullptr;
+  std::vector<uint8_t> mat;             // RS: the encoding matrix
+  std::vector<const uint8_t*> cells;    // [stripe * p + member]: that member's cell of the stripe
 };
 
 namespace {
@@ -422,7 +440,332 @@ int run_stripe(const StripeMap& m, const uint8_t* const* in, uint8_t* const* out
   return REDSET_SUCCESS;
 }
 
+// ---- set verification ----------------------------------------------------
+
+// column window and rows per pass of a wide stripe's check: the scratch is
+// kVerifyRows x kVerifyWindow at most, whatever the set
+constexpr size_t kVerifyWindow = size_t(8) << 20;
+constexpr int kVerifyRows = kMaxOut;
+
+bool verify_fused(const StripeMap& m) {
+  const int nin = static_cast<int>(m.in.size()), nout = static_cast<int>(m.out.size());
+  return m.xor_only ? nin + 1 <= kMaxIn : (nin <= kMaxIn && nout <= kMaxOut);
+}
+
+namespace {
+size_t verify_window(size_t nbytes) { return std::min(kVerifyWindow, (nbytes + 255) & ~size_t(255)); }
+}  // namespace
+
+size_t verify_scratch_bytes(const StripeMap& m, size_t nbytes) {
+  if (verify_fused(m) || m.out.empty()) return 0;
+  return static_cast<size_t>(std::min<int>(kVerifyRows, static_cast<int>(m.out.size()))) * verify_window(nbytes);
+}
+
+int verify_report_reset(unsigned long long* report, int report_rows, int row0, int nrows, void* stream) {
+  return hip_check(static_cast<hipError_t>(reset_report(report, report_rows, row0, nrows, stream)), "report reset");
+}
+
+namespace {
+// one check launch of a single job passed by value
+int check_gf_single(const GfJob& J, int nin, int nout, size_t nbytes, size_t base, unsigned long long* report,
+                    int report_rows, int row0, void* stream) {
+  bool al = true;
+  for (int i = 0; i < nin; ++i) al = al && aligned16(J.in[i]);
+  for (int j = 0; j < nout; ++j) al = al && aligned16(J.out[j]);
+  GfCheckLaunch C;
+  std::memset(&C, 0, sizeof(C));
+  C.g.njobs = 1;
+  C.g.nin = nin;
+  C.g.nout = nout;
+  C.g.bytes_only = al ? 0 : 1;
+  C.g.nbytes = nbytes;
+  C.g.blocks_per_job = blocks_per_job(1, nbytes, gf_blocks_per_cu(nin));
+  C.report = report;
+  C.report_rows = report_rows;
+  C.row0 = row0;
+  C.row_stride = nout;
+  C.base = base;
+  return hip_check(static_cast<hipError_t>(launch_gf_check(C, &J, stream)), "gf_check launch");
+}
+int check_xor_single(const XorJob& J, int nin, size_t nbytes, size_t base, unsigned long long* report,
+                     int report_rows, int row0, void* stream) {
+  bool al = true;
+  for (int i = 0; i < nin; ++i) al = al && aligned16(J.in[i]);
+  XorCheckLaunch C;
+  std::memset(&C, 0, sizeof(C));
+  C.x.njobs = 1;
+  C.x.nin = nin;
+  C.x.bytes_only = al ? 0 : 1;
+  C.x.nbytes = nbytes;
+  C.x.blocks_per_job = blocks_per_job(1, nbytes, xor_blocks_cap());
+  C.report = report;
+  C.report_rows = report_rows;
+  C.row0 = row0;
+  C.row_stride = 1;
+  C.base = base;
+  return hip_check(static_cast<hipError_t>(launch_xor_check(C, &J, stream)), "xor_check launch");
+}
+}  // namespace
+
+int run_verify_stripe(const StripeMap& m, const uint8_t* const* in, const uint8_t* const* stored, size_t nbytes,
+                      size_t base, unsigned long long* report, int report_rows, int row0, uint8_t* scratch,
+                      void* stream, VerifyCount* count) {
+  const int nin = static_cast<int>(m.in.size()), nt = static_cast<int>(m.out.size());
+  if (nt == 0 || nbytes == 0) return REDSET_SUCCESS;
+  if (nin == 0) return fail("stripe with parity but no data cells");
+  if (m.xor_only && nt != 1) return fail("XOR stripe with %d parity cells", nt);
+  if (verify_fused(m)) {
+    if (count) {
+      count->bytes_read += static_cast<unsigned long long>(nin + nt) * nbytes;
+      count->launches += 1;
+      return REDSET_SUCCESS;
+    }
+    if (m.xor_only) {
+      XorJob J;
+      std::memset(&J, 0, sizeof(J));
+      for (int i = 0; i < nin; ++i) J.in[i] = in[i];
+      J.in[nin] = stored[0];
+      return check_xor_single(J, nin + 1, nbytes, base, report, report_rows, row0, stream);
+    }
+    GfJob J;
+    std::memset(&J, 0, sizeof(J));
+    for (int i = 0; i < nin; ++i) J.in[i] = in[i];
+    for (int j = 0; j < nt; ++j) {
+      J.out[j] = const_cast<uint8_t*>(stored[j]);  // only read (gf_check_kernel)
+      for (int i = 0; i < nin; ++i) J.coef[j][i] = m.coef[static_cast<size_t>(j) * nin + i];
+    }
+    return check_gf_single(J, nin, nt, nbytes, base, report, report_rows, row0, stream);
+  }
+  // wide: <= kVerifyRows parity rows of one column window into the scratch
+  // with the combine passes, then the scratch against the stored cells
+  if (!count && !scratch) return fail("wide verify without scratch");
+  const size_t W = verify_window(nbytes);
+  const int passes = (nin + kMaxIn - 1) / kMaxIn;
+  std::vector<const uint8_t*> win(static_cast<size_t>(nin));
+  for (int o0 = 0; o0 < nt; o0 += kVerifyRows) {
+    const int no = std::min(kVerifyRows, nt - o0);
+    StripeMap sub;
+    sub.in = m.in;
+    sub.out.assign(m.out.begin() + o0, m.out.begin() + o0 + no);
+    sub.coef.assign(m.coef.begin() + static_cast<size_t>(o0) * nin, m.coef.begin() + static_cast<size_t>(o0 + no) * nin);
+    sub.xor_only = m.xor_only;
+    for (size_t woff = 0; woff < nbytes; woff += W) {
+      const size_t len = std::min(W, nbytes - woff);
+      if (count) {
+        // every pass reads its inputs and, after the first, the scratch rows
+        // it accumulates into; the check reads the scratch and the stored rows
+        count->bytes_read += (static_cast<unsigned long long>(nin) + static_cast<unsigned long long>(passes - 1) * no +
+                              2ull * no) * len;
+        count->bytes_written += static_cast<unsigned long long>(passes) * no * len;
+        count->launches += passes + 1;
+        continue;
+      }
+      uint8_t* rows[kVerifyRows];
+      for (int j = 0; j < no; ++j) rows[j] = scratch + static_cast<size_t>(j) * W;
+      for (int i = 0; i < nin; ++i) win[static_cast<size_t>(i)] = in[i] + woff;
+      if (int rc = run_stripe(sub, win.data(), rows, len, stream, 0)) return rc;
+      if (m.xor_only) {
+        XorJob J;
+        std::memset(&J, 0, sizeof(J));
+        J.in[0] = rows[0];
+        J.in[1] = stored[0] + woff;
+        if (int rc = check_xor_single(J, 2, len, base + woff, report, report_rows, row0, stream)) return rc;
+      } else {
+        // one input of coefficient 1 per row: parity row j = 1 * scratch row j
+        GfJob J;
+        std::memset(&J, 0, sizeof(J));
+        for (int j = 0; j < no; ++j) {
+          J.in[j] = rows[j];
+          J.out[j] = const_cast<uint8_t*>(stored[o0 + j] + woff);
+          J.coef[j][j] = 1;
+        }
+        if (int rc = check_gf_single(J, no, no, len, base + woff, report, report_rows, row0 + o0, stream)) return rc;
+      }
+    }
+  }
+  return REDSET_SUCCESS;
+}
+
 }  // namespace redset_hip
+
+namespace {
+
+// Whole-set verify plan from the stripes' encode maps. Fused stripes share
+// launches over a device job array: runs of consecutive stripes with the same
+// alignment, so a launch's jobs report to consecutive rows.
+int build_verify_plan(redset_hip_plan* plan, const std::vector<StripeMap>& maps, const SetLayout& L, size_t nbytes) {
+  const int e = plan->info.encoding;
+  plan->report_rows = static_cast<int>(maps.size()) * e;
+  {
+    void* rp = nullptr;
+    const size_t bytes = 2 * static_cast<size_t>(std::max(1, plan->report_rows)) * sizeof(unsigned long long);
+    if (int rc = hip_check(hipMalloc(&rp, bytes), "hipMalloc(verify report)")) return rc;
+    plan->d_report = static_cast<unsigned long long*>(rp);
+  }
+  if (int rc = hip_check(static_cast<hipError_t>(redset_hip::reset_report(plan->d_report, plan->report_rows, 0,
+                                                                          plan->report_rows, nullptr)),
+                         "report reset"))
+    return rc;
+  if (int rc = hip_check(hipStreamSynchronize(nullptr), "report reset")) return rc;
+  redset_hip::VerifyCount cnt;
+  std::vector<GfJob> gall;
+  std::vector<XorJob> xall;
+  size_t scratch = 0;
+  int run_al = -1;  // alignment of the open run of fused stripes
+  for (size_t c = 0; c < maps.size(); ++c) {
+    const StripeMap& m = maps[c];
+    const int nin = static_cast<int>(m.in.size()), nt = static_cast<int>(m.out.size());
+    if (nt != e || nin == 0) return fail("verify: stripe %zu has %d parity and %d data cells", c, nt, nin);
+    if (!redset_hip::verify_fused(m)) {
+      redset_hip_plan::WideStripe w;
+      w.map = m;
+      for (const CellRef& r : m.in) w.in.push_back(L.at(r));
+      for (const CellRef& r : m.out) w.stored.push_back(L.at(r));
+      w.row0 = static_cast<int>(c) * e;
+      scratch = std::max(scratch, redset_hip::verify_scratch_bytes(m, nbytes));
+      if (int rc = redset_hip::run_verify_stripe(m, w.in.data(), w.stored.data(), nbytes, 0, nullptr, 0, 0, nullptr,
+                                                 nullptr, &cnt))
+        return rc;
+      plan->wide.push_back(std::move(w));
+      run_al = -1;
+      continue;
+    }
+    cnt.bytes_read += static_cast<unsigned long long>(nin + nt) * nbytes;
+    bool al = true;
+    if (m.xor_only) {
+      XorJob J;
+      std::memset(&J, 0, sizeof(J));
+      for (int i = 0; i < nin; ++i) J.in[i] = L.at(m.in[i]);
+      J.in[nin] = L.at(m.out[0]);
+      for (int i = 0; i <= nin; ++i) al = al && aligned16(J.in[i]);
+      if (run_al != (al ? 1 : 0)) {
+        redset_hip::XorCheckLaunch C;
+        std::memset(&C, 0, sizeof(C));
+        C.x.jobs = reinterpret_cast<const XorJob*>(xall.size());  // offset, patched below
+        C.x.nin = nin + 1;
+        C.x.bytes_only = al ? 0 : 1;
+        C.x.nbytes = nbytes;
+        C.row0 = static_cast<int>(c) * e;
+        plan->xor_checks.push_back(C);
+        run_al = al ? 1 : 0;
+      }
+      plan->xor_checks.back().x.njobs += 1;
+      xall.push_back(J);
+    } else {
+      GfJob J;
+      std::memset(&J, 0, sizeof(J));
+      for (int i = 0; i < nin; ++i) {
+        J.in[i] = L.at(m.in[i]);
+        al = al && aligned16(J.in[i]);
+      }
+      for (int j = 0; j < nt; ++j) {
+        J.out[j] = L.at(m.out[j]);  // the stored parity: only read
+        al = al && aligned16(J.out[j]);
+        for (int i = 0; i < nin; ++i) J.coef[j][i] = m.coef[static_cast<size_t>(j) * nin + i];
+      }
+      if (run_al != (al ? 1 : 0)) {
+        redset_hip::GfCheckLaunch C;
+        std::memset(&C, 0, sizeof(C));
+        C.g.jobs = reinterpret_cast<const GfJob*>(gall.size());
+        C.g.nin = nin;
+        C.g.nout = nt;
+        C.g.bytes_only = al ? 0 : 1;
+        C.g.nbytes = nbytes;
+        C.row0 = static_cast<int>(c) * e;
+        plan->gf_checks.push_back(C);
+        run_al = al ? 1 : 0;
+      }
+      plan->gf_checks.back().g.njobs += 1;
+      gall.push_back(J);
+    }
+  }
+  // the per-job body only: stripes side by side for small cells, a launch
+  // per stripe for big ones (sequential_jobs, as the plans whose kernels have
+  // no streamed or claimed order)
+  auto shape = [&](auto& C, auto& Lh, int occupancy) {
+    Lh.sequential = sequential_jobs(Lh.njobs, nbytes, false, false, false, false);
+    Lh.group = stripes_per_launch(Lh.sequential);
+    Lh.blocks_per_job = blocks_per_job(jobs_sharing_grid(Lh.sequential, Lh.njobs, Lh.group), nbytes, occupancy);
+    C.report = plan->d_report;
+    C.report_rows = plan->report_rows;
+    C.row_stride = e;
+    C.reset = 1;
+    cnt.launches += launches_of(Lh.sequential, Lh.njobs, Lh.group);
+  };
+  for (auto& C : plan->gf_checks) shape(C, C.g, redset_hip::gf_blocks_per_cu(C.g.nin));
+  for (auto& C : plan->xor_checks) shape(C, C.x, xor_blocks_cap());
+  plan->info.bytes_read = cnt.bytes_read;
+  plan->info.bytes_written = cnt.bytes_written;
+  plan->info.launches = cnt.launches;
+  plan->info.jobs = static_cast<int>(maps.size());
+  if (!gall.empty()) {
+    if (int rc = hip_check(hipMalloc(&plan->d_gf, gall.size() * sizeof(GfJob)), "hipMalloc(plan jobs)")) return rc;
+    if (int rc = hip_check(hipMemcpy(plan->d_gf, gall.data(), gall.size() * sizeof(GfJob), hipMemcpyHostToDevice),
+                           "hipMemcpy(plan jobs)"))
+      return rc;
+    for (auto& C : plan->gf_checks) C.g.jobs = plan->d_gf + reinterpret_cast<uintptr_t>(C.g.jobs);
+  }
+  if (!xall.empty()) {
+    if (int rc = hip_check(hipMalloc(&plan->d_xor, xall.size() * sizeof(XorJob)), "hipMalloc(plan jobs)")) return rc;
+    if (int rc = hip_check(hipMemcpy(plan->d_xor, xall.data(), xall.size() * sizeof(XorJob), hipMemcpyHostToDevice),
+                           "hipMemcpy(plan jobs)"))
+      return rc;
+    for (auto& C : plan->xor_checks) C.x.jobs = plan->d_xor + reinterpret_cast<uintptr_t>(C.x.jobs);
+  }
+  if (scratch > 0) {
+    void* sp = nullptr;
+    if (int rc = hip_check(hipMalloc(&sp, scratch), "hipMalloc(verify scratch)")) return rc;
+    plan->d_scratch = static_cast<uint8_t*>(sp);
+  }
+  return REDSET_SUCCESS;
+}
+
+int finish_verify_plan(int kind, int ranks, int encoding, size_t chunk, const std::vector<StripeMap>& maps,
+                       const SetLayout& L, const redset_hip_rs* rs, redset_hip_plan** out) {
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = kind;
+  plan->info.ranks = ranks;
+  plan->info.encoding = encoding;
+  plan->info.chunk_size = chunk;
+  plan->cells.resize(static_cast<size_t>(ranks) * ranks);
+  for (int c = 0; c < ranks; ++c)
+    for (int s = 0; s < ranks; ++s) {
+      const CellRef cell = rs ? redset_hip::rs_cell(rs, s, c)
+                              : (s == c ? CellRef{s, redset_hip::kParity, 0}
+                                        : CellRef{s, redset_hip::kData, redset_hip::xor_segment(s, c)});
+      plan->cells[static_cast<size_t>(c) * ranks + s] = L.at(cell);
+    }
+  if (rs) plan->mat = rs->mat;
+  if (int rc = build_verify_plan(plan, maps, L, chunk)) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+bool is_verify(const redset_hip_plan* plan) {
+  return plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY || plan->info.kind == REDSET_HIP_PLAN_XOR_VERIFY;
+}
+
+// the plan's report as rows, ordered on `stream` after the work there
+int read_report(const redset_hip_plan* plan, void* stream, std::vector<redset_hip_verify_row>& rows) {
+  const size_t n = static_cast<size_t>(plan->report_rows);
+  std::vector<unsigned long long> raw(2 * n);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n > 0)
+    if (int rc = hip_check(hipMemcpyAsync(raw.data(), plan->d_report, raw.size() * sizeof(unsigned long long),
+                                          hipMemcpyDeviceToHost, s),
+                           "verify report copy"))
+      return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "verify report sync")) return rc;
+  rows.resize(n);
+  for (size_t i = 0; i < n; ++i) rows[i] = redset_hip_verify_row{raw[i], raw[n + i]};
+  return REDSET_SUCCESS;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -585,8 +928,133 @@ int redset_hip_plan_combine(const redset_hip_combine_job* jobs, int njobs, size_
   return finish_plan(0, 0, 0, 0, nbytes, maps, SetLayout{table.data(), table.data(), 0}, out);
 }
 
+int redset_hip_rs_plan_verify(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                              size_t chunk_size, size_t stride, redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  std::vector<StripeMap> maps(rs->ranks);
+  for (int c = 0; c < rs->ranks; ++c) redset_hip::rs_verify_map(rs, c, maps[c]);
+  return finish_verify_plan(REDSET_HIP_PLAN_RS_VERIFY, rs->ranks, rs->encoding, chunk_size, maps,
+                            SetLayout{lofi, parity, stride}, rs, out);
+}
+
+int redset_hip_xor_plan_verify(int ranks, unsigned char* const* lofi, unsigned char* const* xorc, size_t chunk_size,
+                               size_t stride, redset_hip_plan** out) {
+  if (ranks < 2) return fail("XOR needs at least 2 ranks, got %d", ranks);
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(xorc),
+                              ranks, chunk_size, stride, out))
+    return rc;
+  std::vector<StripeMap> maps(ranks);
+  for (int c = 0; c < ranks; ++c) redset_hip::xor_encode_map(ranks, c, maps[c]);
+  return finish_verify_plan(REDSET_HIP_PLAN_XOR_VERIFY, ranks, 1, chunk_size, maps, SetLayout{lofi, xorc, stride},
+                            nullptr, out);
+}
+
+int redset_hip_plan_verify_report(const redset_hip_plan* plan, void* stream, redset_hip_verify_row* rows, int nrows,
+                                  unsigned long long* total_mismatch_bytes) {
+  if (!plan) return fail("verify_report: null plan");
+  if (!is_verify(plan)) return fail("verify_report: not a verify plan (kind %d)", plan->info.kind);
+  if (rows && nrows < plan->report_rows)
+    return fail("verify_report: room for %d rows, the plan reports %d", nrows, plan->report_rows);
+  std::vector<redset_hip_verify_row> got;
+  if (int rc = read_report(plan, stream, got)) return rc;
+  unsigned long long total = 0;
+  for (size_t i = 0; i < got.size(); ++i) {
+    total += got[i].mismatch_bytes;
+    if (rows) rows[i] = got[i];
+  }
+  if (total_mismatch_bytes) *total_mismatch_bytes = total;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_locate_syndrome(const redset_hip_rs* rs, int chunk_id, const unsigned char* syndrome,
+                                  int* member_out) {
+  if (!rs || !syndrome || !member_out) return fail("locate_syndrome: null argument");
+  const int p = rs->ranks, e = rs->encoding;
+  if (chunk_id < 0 || chunk_id >= p) return fail("locate_syndrome: chunk id %d out of range", chunk_id);
+  *member_out = -1;
+  int nz = 0, only = -1;
+  for (int j = 0; j < e; ++j)
+    if (syndrome[j]) ++nz, only = j;
+  if (e < 2 || nz == 0) return REDSET_SUCCESS;
+  if (nz == 1) {
+    // the holder of parity row `only`: member (chunk_id - only) mod p
+    for (int r = 0; r < p; ++r)
+      if (redset_hip::encoding_id(p, e, r, chunk_id) == p + only) *member_out = r;
+    return REDSET_SUCCESS;
+  }
+  const redset_hip::Field& F = redset_hip::field();
+  int found = -1, matches = 0;
+  for (int m = 0; m < p; ++m) {
+    if (redset_hip::encoding_id(p, e, m, chunk_id) >= p) continue;  // holds parity in this stripe
+    int j0 = -1;
+    for (int j = 0; j < e && j0 < 0; ++j)
+      if (rs->mat[static_cast<size_t>(p + j) * p + m]) j0 = j;
+    if (j0 < 0) continue;
+    const uint8_t x = F.mul(syndrome[j0], F.inv(rs->mat[static_cast<size_t>(p + j0) * p + m]));
+    bool ok = x != 0;
+    for (int j = 0; j < e && ok; ++j) ok = F.mul(rs->mat[static_cast<size_t>(p + j) * p + m], x) == syndrome[j];
+    if (ok) found = m, ++matches;
+  }
+  if (matches == 1) *member_out = found;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int stripe, int* member_out,
+                                  unsigned long long* offset_out) {
+  if (!plan || !member_out || !offset_out) return fail("verify_locate: null argument");
+  if (!is_verify(plan)) return fail("verify_locate: not a verify plan (kind %d)", plan->info.kind);
+  const int p = plan->info.ranks, e = plan->info.encoding;
+  if (stripe < 0 || stripe >= p) return fail("verify_locate: stripe %d out of range", stripe);
+  *member_out = -1;
+  *offset_out = ~0ull;
+  std::vector<redset_hip_verify_row> rows;
+  if (int rc = read_report(plan, stream, rows)) return rc;
+  unsigned long long off = ~0ull;
+  for (int i = 0; i < e; ++i) {
+    const redset_hip_verify_row& r = rows[static_cast<size_t>(stripe) * e + i];
+    if (r.mismatch_bytes) off = std::min(off, r.first_offset);
+  }
+  *offset_out = off;
+  if (off == ~0ull || plan->info.kind != REDSET_HIP_PLAN_RS_VERIFY) return REDSET_SUCCESS;
+  // the stripe's byte column at that offset, member by member
+  std::vector<uint8_t> col(static_cast<size_t>(p));
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int m = 0; m < p; ++m)
+    if (int rc = hip_check(hipMemcpyAsync(&col[m], plan->cells[static_cast<size_t>(stripe) * p + m] + off, 1,
+                                          hipMemcpyDeviceToHost, s),
+                           "verify_locate copy"))
+      return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "verify_locate sync")) return rc;
+  const redset_hip::Field& F = redset_hip::field();
+  std::vector<uint8_t> syn(static_cast<size_t>(e), 0);
+  for (int m = 0; m < p; ++m) {
+    const int enc = redset_hip::encoding_id(p, e, m, stripe);
+    if (enc >= p) {
+      syn[enc - p] ^= col[m];
+      continue;
+    }
+    for (int j = 0; j < e; ++j) syn[j] ^= F.mul(plan->mat[static_cast<size_t>(p + j) * p + m], col[m]);
+  }
+  redset_hip_rs rs{p, e, plan->mat};
+  return redset_hip_rs_locate_syndrome(&rs, stripe, syn.data(), member_out);
+}
+
 int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   if (!plan) return fail("null plan");
+  for (const auto& C : plan->gf_checks)
+    if (int e = redset_hip::launch_gf_check(C, nullptr, stream)) return hip_check(static_cast<hipError_t>(e), "gf_check launch");
+  for (const auto& C : plan->xor_checks)
+    if (int e = redset_hip::launch_xor_check(C, nullptr, stream)) return hip_check(static_cast<hipError_t>(e), "xor_check launch");
+  for (const auto& w : plan->wide) {
+    const int rows = static_cast<int>(w.stored.size());
+    if (int rc = redset_hip::verify_report_reset(plan->d_report, plan->report_rows, w.row0, rows, stream)) return rc;
+    if (int rc = redset_hip::run_verify_stripe(w.map, w.in.data(), w.stored.data(), plan->info.chunk_size, 0,
+                                               plan->d_report, plan->report_rows, w.row0, plan->d_scratch, stream))
+      return rc;
+  }
   for (const GfLaunch& G : plan->gf_launches)
     if (int e = redset_hip::launch_gf(G, stream)) return hip_check(static_cast<hipError_t>(e), "gf_mac launch");
   for (const XorLaunch& X : plan->xor_launches)
@@ -605,6 +1073,8 @@ void redset_hip_plan_destroy(redset_hip_plan* plan) {
   if (plan->d_gf) (void) hipFree(plan->d_gf);
   if (plan->d_xor) (void) hipFree(plan->d_xor);
   if (plan->d_claim) (void) hipFree(plan->d_claim);
+  if (plan->d_report) (void) hipFree(plan->d_report);
+  if (plan->d_scratch) (void) hipFree(plan->d_scratch);
   delete plan;
 }
 

@@ -552,6 +552,257 @@ int run_pipeline(const std::vector<StripeMap>& maps, size_t chunk, size_t slice,
   return REDSET_SUCCESS;
 }
 
+// Set verification of a host-resident set (include/redset_hip.h
+// redset_hip_*_verify_stream): run_pipeline's read -> H2D -> kernel stages
+// with the check kernels (stripe_map.h run_verify_stripe) and nothing after
+// them -- no D2H, no write; a slot returns to the reader once its kernels are
+// done. `maps` are the stripes' ENCODE maps: a unit reads the data cells and
+// the stored parity cells alike. The report lives in device memory for the
+// call: reset once, every slice adds to its stripe's rows with its own cell
+// offset as base, read back after the last sync. Page-locked cells
+// (io->map over whole cells) are checked in place, one pass per stripe.
+int run_verify(const std::vector<StripeMap>& maps, int e, size_t chunk, size_t slice, int io_threads,
+               const redset_hip_io* io, redset_hip_stream_stats* stats, redset_hip_verify_row* rows, int nrows) {
+  const int want = static_cast<int>(maps.size()) * e;
+  if (!rows || nrows < want) return fail("verify_stream: room for %d report rows, the call reports %d", rows ? nrows : 0, want);
+  if (!io || !io->read) return fail("null redset_hip_io");
+  redset_hip_stream_stats st;
+  std::memset(&st, 0, sizeof(st));
+  for (int i = 0; i < want; ++i) rows[i] = redset_hip_verify_row{0, ~0ull};
+  if (chunk == 0 || want == 0) {
+    if (stats) *stats = st;
+    return REDSET_SUCCESS;
+  }
+  if (slice == 0) slice = chunk > (8u << 20) ? (8u << 20) : std::max<size_t>(256u << 10, chunk / 16);
+  slice = std::min(slice, std::max<size_t>(chunk, 1));
+  slice = (slice + 255) & ~static_cast<size_t>(255);
+  if (io_threads <= 0) io_threads = 8;
+  const double t0 = now_s();
+
+  // zero copy: every cell page-locked and contiguous (see try_zero_copy)
+  bool mapped = io->map != nullptr;
+#if REDSET_HIP_TEST_KNOBS
+  {
+    const char* env = std::getenv("REDSET_HIP_ZERO_COPY");
+    if (env && env[0] == '0') mapped = false;
+  }
+#endif
+  std::vector<std::vector<const uint8_t*>> zin(maps.size()), zout(maps.size());
+  auto dev = [&](const CellRef& c) -> const uint8_t* {
+    void* h0 = io->map(io->ctx, c.rank, c.kind, c.index, 0);
+    void* h1 = io->map(io->ctx, c.rank, c.kind, c.index, chunk - 1);
+    if (!h0 || static_cast<char*>(h1) != static_cast<char*>(h0) + (chunk - 1)) return nullptr;
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, h0, 0) != hipSuccess) {
+      (void) hipGetLastError();
+      return nullptr;
+    }
+    return static_cast<const uint8_t*>(d);
+  };
+  for (size_t k = 0; k < maps.size() && mapped; ++k) {
+    for (const CellRef& c : maps[k].in) {
+      const uint8_t* d = mapped ? dev(c) : nullptr;
+      mapped = mapped && d;
+      zin[k].push_back(d);
+    }
+    for (const CellRef& c : maps[k].out) {
+      const uint8_t* d = mapped ? dev(c) : nullptr;
+      mapped = mapped && d;
+      zout[k].push_back(d);
+    }
+  }
+
+  size_t max_cells = 0, scratch_n = 0;
+  for (const StripeMap& m : maps) {
+    max_cells = std::max(max_cells, m.in.size() + m.out.size());
+    scratch_n = std::max(scratch_n, redset_hip::verify_scratch_bytes(m, mapped ? chunk : slice));
+  }
+  std::vector<Unit> units;
+  if (!mapped)
+    for (size_t k = 0; k < maps.size(); ++k)
+      for (size_t off = 0; off < chunk; off += slice) units.push_back(Unit{static_cast<int>(k), off, std::min(slice, chunk - off)});
+
+  Slot slots[kSlots];
+  ResourceCache& cache = ResourceCache::get();
+  hipStream_t s_in = mapped ? nullptr : cache.take_stream(), s_comp = cache.take_stream();
+  int rc = ((mapped || s_in) && s_comp) ? 0 : fail("hipStreamCreate failed");
+  unsigned hang0 = 0;
+  rc = rc ? rc : hang_mark(s_comp, &hang0);
+  uint8_t *d_report = nullptr, *d_scratch = nullptr;
+  size_t n_report = 0, n_scratch = 0;
+  auto buf = [&](uint8_t** p, size_t* have, size_t n, bool on_dev) {
+    if (rc) return;
+    *p = static_cast<uint8_t*>(cache.take_buf(n, on_dev, have));
+    if (!*p) rc = fail("%s(%zu) failed", on_dev ? "hipMalloc" : "hipHostMalloc", n);
+  };
+  buf(&d_report, &n_report, 2 * static_cast<size_t>(want) * sizeof(unsigned long long), true);
+  if (scratch_n) buf(&d_scratch, &n_scratch, scratch_n, true);
+  unsigned long long* const report = reinterpret_cast<unsigned long long*>(d_report);
+  rc = rc ? rc : redset_hip::verify_report_reset(report, want, 0, want, s_comp);
+
+  std::atomic<int> io_err(0);
+  std::atomic<long long> read_ns(0);
+  double gpu_s = 0;
+  if (mapped) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    rc = rc ? rc : hip_ok(hipEventCreate(&e0), "event");
+    rc = rc ? rc : hip_ok(hipEventCreate(&e1), "event");
+    rc = rc ? rc : hip_ok(hipEventRecord(e0, s_comp), "event record");
+    for (size_t k = 0; k < maps.size() && rc == 0; ++k) {
+      rc = redset_hip::run_verify_stripe(maps[k], zin[k].data(), zout[k].data(), chunk, 0, report, want,
+                                         static_cast<int>(k) * e, d_scratch, s_comp);
+      st.bytes_read += (maps[k].in.size() + maps[k].out.size()) * chunk;
+      st.units += 1;
+    }
+    rc = rc ? rc : hip_ok(hipEventRecord(e1, s_comp), "event record");
+    rc = rc ? rc : hip_ok(hipStreamSynchronize(s_comp), "stream synchronize");
+    float ms = 0;
+    if (rc == 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) gpu_s = ms * 1e-3;
+    if (e0) (void) hipEventDestroy(e0);
+    if (e1) (void) hipEventDestroy(e1);
+  } else {
+    for (Slot& S : slots) {
+      buf(&S.h_in, &S.n_h_in, max_cells * slice, false);
+      buf(&S.d_in, &S.n_d_in, max_cells * slice, true);
+      rc = rc ? rc : hip_ok(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming), "event");
+      rc = rc ? rc : hip_ok(hipEventCreate(&S.ev_start), "event");
+      rc = rc ? rc : hip_ok(hipEventCreate(&S.ev_done), "event");
+    }
+  }
+  const size_t nunits = units.size();
+  if (rc == 0 && !mapped) {
+    std::mutex mu;
+    std::condition_variable cv;
+    IoPool rpool(io_threads);
+    std::atomic<bool> abort(false);
+    auto wait_state = [&](Slot& S, SlotState w) {
+      std::unique_lock<std::mutex> lk(mu);
+      cv.wait(lk, [&] { return S.state == w || abort.load(); });
+      return !abort.load();
+    };
+    auto stop = [&] {
+      {
+        std::lock_guard<std::mutex> g(mu);
+        abort = true;
+      }
+      cv.notify_all();
+    };
+    auto set_state = [&](Slot& S, SlotState v) {
+      {
+        std::lock_guard<std::mutex> g(mu);
+        S.state = v;
+      }
+      cv.notify_all();
+    };
+    // cell i of a unit: the map's data cells, then its stored parity cells
+    auto cell_of = [&](const StripeMap& m, size_t i) -> const CellRef& {
+      return i < m.in.size() ? m.in[i] : m.out[i - m.in.size()];
+    };
+    std::thread reader([&] {
+      for (size_t u = 0; u < nunits; ++u) {
+        Slot& S = slots[u % kSlots];
+        if (!wait_state(S, kFree)) return;
+        const Unit U = units[u];
+        const StripeMap& m = maps[U.map];
+        const size_t nc = m.in.size() + m.out.size();
+        S.src.assign(nc, nullptr);
+        if (io->map)
+          for (size_t i = 0; i < nc; ++i) {
+            const CellRef& c = cell_of(m, i);
+            S.src[i] = io->map(io->ctx, c.rank, c.kind, c.index, U.off);
+          }
+        std::vector<std::function<void()>> tasks;
+        for (size_t i = 0; i < nc; ++i) {
+          if (S.src[i]) continue;  // DMAed straight from mapped host memory
+          tasks.push_back([&, i, U] {
+            const CellRef& c = cell_of(maps[U.map], i);
+            const double a = now_s();
+            if (io->read(io->ctx, c.rank, c.kind, c.index, U.off, U.len, S.h_in + i * slice) != 0) io_err = 1;
+            read_ns += static_cast<long long>((now_s() - a) * 1e9);
+          });
+        }
+        rpool.run(tasks);
+        S.unit = u;
+        set_state(S, kRead);
+      }
+    });
+    // frees a slot once its unit's kernels are done
+    std::thread releaser([&] {
+      for (size_t u = 0; u < nunits; ++u) {
+        Slot& S = slots[u % kSlots];
+        if (!wait_state(S, kOnGpu)) return;
+        if (hipEventSynchronize(S.ev_done) != hipSuccess) {
+          io_err = 2;
+          stop();
+          return;
+        }
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, S.ev_start, S.ev_done) == hipSuccess) gpu_s += ms * 1e-3;
+        set_state(S, kFree);
+      }
+    });
+    std::vector<const uint8_t*> ins, outs;
+    for (size_t u = 0; u < nunits && rc == 0; ++u) {
+      Slot& S = slots[u % kSlots];
+      if (!wait_state(S, kRead)) break;
+      const Unit& U = units[u];
+      const StripeMap& m = maps[U.map];
+      const size_t nin = m.in.size(), nout = m.out.size();
+      rc = rc ? rc : hip_ok(hipEventRecord(S.ev_start, s_in), "event record");
+      for (size_t i = 0; i < nin + nout && rc == 0; ++i) {
+        const void* from = S.src[i] ? S.src[i] : S.h_in + i * slice;
+        rc = hip_ok(hipMemcpyAsync(S.d_in + i * slice, from, U.len, hipMemcpyHostToDevice, s_in), "H2D");
+      }
+      rc = rc ? rc : hip_ok(hipEventRecord(S.ev_in, s_in), "event record");
+      rc = rc ? rc : hip_ok(hipStreamWaitEvent(s_comp, S.ev_in, 0), "stream wait");
+      ins.resize(nin);
+      outs.resize(nout);
+      for (size_t i = 0; i < nin; ++i) ins[i] = S.d_in + i * slice;
+      for (size_t j = 0; j < nout; ++j) outs[j] = S.d_in + (nin + j) * slice;
+      if (rc == 0)
+        rc = redset_hip::run_verify_stripe(m, ins.data(), outs.data(), U.len, U.off, report, want, U.map * e, d_scratch,
+                                           s_comp);
+      rc = rc ? rc : hip_ok(hipEventRecord(S.ev_done, s_comp), "event record");
+      if (rc != 0) break;
+      st.bytes_read += (nin + nout) * U.len;
+      st.units += 1;
+      set_state(S, kOnGpu);
+    }
+    if (rc != 0) stop();
+    reader.join();
+    releaser.join();
+  }
+  bool ok = rc == 0 && io_err.load() != 2;
+  for (hipStream_t s : {s_in, s_comp})
+    if (s && hipStreamSynchronize(s) != hipSuccess) ok = false;
+  if (ok) rc = hang_check(s_comp, hang0);
+  if (ok && rc == 0 && io_err.load() == 0) {
+    std::vector<unsigned long long> raw(2 * static_cast<size_t>(want));
+    rc = hip_ok(hipMemcpy(raw.data(), report, raw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost),
+                "verify report copy");
+    for (int i = 0; i < want && rc == 0; ++i) rows[i] = redset_hip_verify_row{raw[i], raw[static_cast<size_t>(want) + i]};
+  }
+  cache.give_buf(d_report, n_report, true, ok);
+  cache.give_buf(d_scratch, n_scratch, true, ok);
+  for (Slot& S : slots) {
+    cache.give_buf(S.h_in, S.n_h_in, false, ok);
+    cache.give_buf(S.d_in, S.n_d_in, true, ok);
+    if (S.ev_in) (void) hipEventDestroy(S.ev_in);
+    if (S.ev_start) (void) hipEventDestroy(S.ev_start);
+    if (S.ev_done) (void) hipEventDestroy(S.ev_done);
+  }
+  cache.give_stream(s_in, ok);
+  cache.give_stream(s_comp, ok);
+  st.seconds = now_s() - t0;
+  st.read_seconds = read_ns.load() * 1e-9;
+  st.gpu_seconds = gpu_s;
+  if (stats) *stats = st;
+  if (rc) return rc;
+  if (io_err.load() == 2) return fail("verify pipeline: a device wait failed");
+  if (io_err.load()) return fail("stream I/O callback failed");
+  return REDSET_SUCCESS;
+}
+
 int stripe_range(int ranks, int first, int n, int& lo, int& hi) {
   if (n <= 0) {
     first = 0;
@@ -741,6 +992,28 @@ int redset_hip_xor_rebuild_stream(int ranks, int root, size_t chunk_size, int fi
   for (int c = lo; c < hi; ++c)
     if (int rc = redset_hip::xor_rebuild_map(ranks, root, c, maps[c - lo])) return rc;
   return run_pipeline(maps, chunk_size, slice_bytes, io_threads, io, stats);
+}
+
+int redset_hip_rs_verify_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                size_t slice_bytes, int io_threads, const redset_hip_io* io,
+                                redset_hip_stream_stats* stats, redset_hip_verify_row* rows, int nrows) {
+  if (!rs) return fail("null rs state");
+  int lo, hi;
+  if (int rc = stripe_range(rs->ranks, first_stripe, nstripes, lo, hi)) return rc;
+  std::vector<StripeMap> maps(hi - lo);
+  for (int c = lo; c < hi; ++c) redset_hip::rs_verify_map(rs, c, maps[c - lo]);
+  return run_verify(maps, rs->encoding, chunk_size, slice_bytes, io_threads, io, stats, rows, nrows);
+}
+
+int redset_hip_xor_verify_stream(int ranks, size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
+                                 int io_threads, const redset_hip_io* io, redset_hip_stream_stats* stats,
+                                 redset_hip_verify_row* rows, int nrows) {
+  if (ranks < 2) return fail("XOR needs at least 2 ranks, got %d", ranks);
+  int lo, hi;
+  if (int rc = stripe_range(ranks, first_stripe, nstripes, lo, hi)) return rc;
+  std::vector<StripeMap> maps(hi - lo);
+  for (int c = lo; c < hi; ++c) redset_hip::xor_encode_map(ranks, c, maps[c - lo]);
+  return run_verify(maps, 1, chunk_size, slice_bytes, io_threads, io, stats, rows, nrows);
 }
 
 int redset_hip_hostio_create(int ranks, unsigned char* const* lofi, unsigned char* const* parity, size_t cell_stride,

@@ -49,6 +49,19 @@ int rs_encode_map(const redset_hip_rs* rs, int c, StripeMap& m) {
   return 0;
 }
 
+int rs_verify_map(const redset_hip_rs* rs, int c, StripeMap& m) {
+  StripeMap enc;
+  if (int rc = rs_encode_map(rs, c, enc)) return rc;
+  const size_t nin = enc.in.size(), nout = enc.out.size();
+  m = enc;
+  for (size_t j = 0; j < nout; ++j) {
+    const size_t row = static_cast<size_t>(enc.out[j].index);  // slot i holds row p + i
+    m.out[row] = enc.out[j];
+    for (size_t i = 0; i < nin; ++i) m.coef[row * nin + i] = enc.coef[j * nin + i];
+  }
+  return 0;
+}
+
 int rs_decode_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk,
                      std::vector<uint8_t>& D) {
   const int p = rs->ranks, e = rs->encoding;

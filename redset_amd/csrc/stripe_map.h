@@ -4,6 +4,7 @@
 // (redset_hip.cpp) and the host streaming pipeline (stream_pipeline.cpp).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -41,6 +42,11 @@ CellRef rs_cell(const redset_hip_rs* rs, int rank, int chunk);
 // (c - i) mod p's slot i). src/redset_reedsolomon.c:329-376.
 int rs_encode_map(const redset_hip_rs* rs, int c, StripeMap& m);
 
+// RS verify of stripe c: the encode map with its outputs in parity-row order
+// (out[i] = the stored cell of row p+i, member (c - i) mod p's slot i), so
+// that output i reports to the stripe's report row i.
+int rs_verify_map(const redset_hip_rs* rs, int c, StripeMap& m);
+
 // RS rebuild of stripe c: the lost members' cells from the surviving cells
 // with a nonzero decode coefficient. Reproduces redset_rs_reduce_decode +
 // redset_rs_gaussian_solve (common.c:855-899, :570-630) as one linear map.
@@ -64,5 +70,28 @@ const char* last_error();
 // accumulate: XOR into the outputs instead of overwriting them.
 int run_stripe(const StripeMap& m, const uint8_t* const* in, uint8_t* const* out, size_t nbytes, void* stream,
                int blocks_total, bool accumulate = false);
+
+// Set verification of one stripe (redset_hip.cpp). `m` is the stripe's ENCODE
+// map (in: the data cells, out: the parity cells); in[i] / stored[j] are the
+// device pointers of those cells' bytes [base, base + nbytes): the check
+// kernels compare the parity of in[] with stored[] and add what differs to
+// rows [row0, row0 + m.out.size()) of `report` (codec_kernels.h
+// GfCheckLaunch), which the caller has reset. Fused (verify_fused: <= 16
+// inputs and <= 4 parity rows; XOR: <= 16 cells) it is one launch that writes
+// nothing; wider maps compute <= 4 rows at a time into `scratch`
+// (verify_scratch_bytes, at most 32 MiB) in column windows of <= 8 MiB and
+// check those. With `count` set nothing is launched: only the algorithmic
+// bytes and launches are tallied.
+struct VerifyCount {
+  unsigned long long bytes_read = 0, bytes_written = 0;
+  int launches = 0;
+};
+bool verify_fused(const StripeMap& m);
+size_t verify_scratch_bytes(const StripeMap& m, size_t nbytes);
+int run_verify_stripe(const StripeMap& m, const uint8_t* const* in, const uint8_t* const* stored, size_t nbytes,
+                      size_t base, unsigned long long* report, int report_rows, int row0, uint8_t* scratch,
+                      void* stream, VerifyCount* count = nullptr);
+// rows [row0, row0 + nrows) of a device report to "nothing differs" on `stream`; REDSET_* code
+int verify_report_reset(unsigned long long* report, int report_rows, int row0, int nrows, void* stream);
 
 }  // namespace redset_hip

@@ -100,15 +100,11 @@ def _apply_meta(path: str, meta: H.Tree) -> List[str]:
     return errs
 
 
-def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
-    """Rebuild the lost members of one set from the redundancy files that can
-    still be read (``redundancy_files`` may name lost ones too). A member is
-    lost when its redundancy file is unreadable or shorter than header + k
-    chunks, or one of its data files is absent or the wrong size. More lost
-    members than the scheme tolerates is an error
-    (src/redset_reedsolomon_serial.c:496-519). Lost members get
-    their data files, file metadata and redundancy file (header regenerated
-    from the set facts, so it matches what apply_set wrote) back."""
+def _read_set(redundancy_files: Sequence[str]):
+    """The set as its readable redundancy files' headers describe it: the
+    facts, every member's redundancy file name and data files, and the lost
+    members (redundancy file unreadable or shorter than header + k chunks, or
+    a data file absent or the wrong size)."""
     heads, paths = [], {}
     for path in redundancy_files:
         try:
@@ -138,6 +134,20 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
             return False
 
     lost = [r for r in range(p) if not f.have_header[r] or not parity_ok(r) or not _files_ok(files[r])]
+    return f, reds, files, lost
+
+
+def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
+    """Rebuild the lost members of one set from the redundancy files that can
+    still be read (``redundancy_files`` may name lost ones too). A member is
+    lost when its redundancy file is unreadable or shorter than header + k
+    chunks, or one of its data files is absent or the wrong size. More lost
+    members than the scheme tolerates is an error
+    (src/redset_reedsolomon_serial.c:496-519). Lost members get
+    their data files, file metadata and redundancy file (header regenerated
+    from the set facts, so it matches what apply_set wrote) back."""
+    f, reds, files, lost = _read_set(redundancy_files)
+    p, k = f.ranks, f.encoding
     out = {"scheme": f.scheme, "ranks": p, "encoding": k, "chunk": f.chunk, "missing": lost,
            "redundancy": reds, "errors": []}
     if not lost:
@@ -169,4 +179,87 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
             (_, meta), = f.members[r]["FILE"][str(i)].items()
             out["errors"] += _apply_meta(path, meta)
     out["ok"] = not out["errors"]
+    return out
+
+
+def _gf_mul(a: int, b: int) -> int:
+    """GF(2^8) / 0x11D product (the codec's field)."""
+    r = 0
+    while b:
+        if b & 1:
+            r ^= a
+        b >>= 1
+        a <<= 1
+        if a & 0x100:
+            a ^= 0x11D
+    return r
+
+
+def _cell_byte(files, red: str, header: int, chunk: int, kind_data: bool, index: int, off: int) -> int:
+    """One byte of a member's cell: logical-file offset index*chunk + off over
+    its data files (zeros past the last), or its redundancy file's slot."""
+    if not kind_data:
+        with open(red, "rb") as fh:
+            fh.seek(header + index * chunk + off)
+            return fh.read(1)[0]
+    pos = index * chunk + off
+    for path, size in files:
+        if pos < size:
+            with open(path, "rb") as fh:
+                fh.seek(pos)
+                return fh.read(1)[0]
+        pos -= size
+    return 0
+
+
+def verify_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
+    """Scrub one set on disk: stream every member's data files and parity
+    chunks through the check kernels (redset_amd.stream.*_verify_stream;
+    nothing is written) and report whether the stored parity still matches
+    the stored data. Driven by the headers as rebuild_set is; every member
+    must be present (a lost member is rebuild_set's job, and a ValueError
+    here). Returns the scheme, ``clean``, ``mismatch_bytes`` (summed over the
+    parity rows) and ``damaged``: per damaged stripe its number, the first
+    differing cell ``offset``, the located ``member`` (None for XOR sets or
+    when no single member explains the column) and whether that member's
+    wrong cell is ``"data"`` or ``"parity"``. A located member is repaired by
+    removing its files and calling rebuild_set."""
+    f, reds, files, lost = _read_set(redundancy_files)
+    p, k = f.ranks, f.encoding
+    if lost:
+        raise ValueError(f"members {lost} are lost: rebuild_set them before verifying")
+    hsize = [f.header_size[r] for r in range(p)]
+    codec = _codec(f.scheme, p, k)
+    io = stream.FileIO(files, reds, hsize, f.chunk)
+    try:
+        if f.scheme == "RS":
+            res = stream.rs_verify_stream(codec, f.chunk, io, slice_bytes=slice_bytes)
+        else:
+            res = stream.xor_verify_stream(p, f.chunk, io, slice_bytes=slice_bytes)
+    finally:
+        io.close()
+    mism, first = res["mismatch"], res["first"]
+    out = {"scheme": f.scheme, "ranks": p, "encoding": k, "chunk": f.chunk, "clean": bool(res["clean"]),
+           "mismatch_bytes": int(mism.sum()), "damaged": [], "stats": res["stats"]}
+    mat = codec.matrix() if codec is not None else None
+    for c in range(p):
+        if not mism[c].any():
+            continue
+        off = int(min(int(first[c, i]) for i in range(mism.shape[1]) if mism[c, i]))
+        entry = {"stripe": c, "offset": off, "member": None, "kind": None}
+        if codec is not None:
+            syn = [0] * k
+            for s in range(p):
+                enc = codec.encoding_id(s, c)
+                if enc < p:
+                    b = _cell_byte(files[s], reds[s], hsize[s], f.chunk, True, codec.data_id(s, c), off)
+                    for j in range(k):
+                        syn[j] ^= _gf_mul(int(mat[p + j, s]), b)
+                else:
+                    syn[enc - p] ^= _cell_byte(files[s], reds[s], hsize[s], f.chunk, False, enc - p, off)
+            m = codec.locate_syndrome(c, syn)
+            if m >= 0:
+                entry["member"] = m
+                entry["kind"] = "data" if codec.encoding_id(m, c) < p else "parity"
+        out["damaged"].append(entry)
     return out

@@ -94,6 +94,33 @@ def xor_rebuild_stream(ranks: int, root: int, chunk: int, io, first: int = 0, ns
                 io_threads, ctypes.byref(io.io))
 
 
+def _verify(fn, stripes: int, e: int, *args) -> dict:
+    from .codec import rows_to_arrays
+
+    st = _lib.StreamStats()
+    rows = (_lib.VerifyRow * max(1, stripes * e))()
+    _lib.check(fn(*args, ctypes.byref(st), rows, stripes * e), fn.__name__)
+    mism, first = rows_to_arrays(rows[:stripes * e], stripes, e)
+    return {"mismatch": mism, "first": first, "clean": not mism.any(), "stats": st.as_dict()}
+
+
+def rs_verify_stream(codec, chunk: int, io, first: int = 0, nstripes: int = 0, slice_bytes: int = 0,
+                     io_threads: int = 0) -> dict:
+    """Verify a host-resident RS set: ``mismatch`` / ``first`` arrays
+    [stripes of the call, e] (see codec.VerifyPlan.report), ``clean`` and the
+    pipeline statistics. Reads only; io's write is never called."""
+    n = nstripes if nstripes > 0 else codec.ranks
+    return _verify(_lib.load().redset_hip_rs_verify_stream, n, codec.encoding, codec._h, chunk, first, nstripes,
+                   slice_bytes, io_threads, ctypes.byref(io.io))
+
+
+def xor_verify_stream(ranks: int, chunk: int, io, first: int = 0, nstripes: int = 0, slice_bytes: int = 0,
+                      io_threads: int = 0) -> dict:
+    n = nstripes if nstripes > 0 else ranks
+    return _verify(_lib.load().redset_hip_xor_verify_stream, n, 1, ranks, chunk, first, nstripes, slice_bytes,
+                   io_threads, ctypes.byref(io.io))
+
+
 def chunk_size_for(max_bytes: int, data_cells: int) -> int:
     """redset_apply_rs / redset_apply_xor chunk size: ceil(max / data cells),
     at least 1 (src/redset_reedsolomon.c:485-493, src/redset_xor.c:362-370)."""
