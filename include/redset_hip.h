@@ -49,7 +49,8 @@ enum {
   REDSET_HIP_PLAN_XOR_ENCODE = 3,
   REDSET_HIP_PLAN_XOR_REBUILD = 4,
   REDSET_HIP_PLAN_RS_VERIFY = 5,
-  REDSET_HIP_PLAN_XOR_VERIFY = 6
+  REDSET_HIP_PLAN_XOR_VERIFY = 6,
+  REDSET_HIP_PLAN_CRC32 = 7
 };
 
 typedef struct {
@@ -191,6 +192,39 @@ int redset_hip_rs_locate_syndrome(const redset_hip_rs* rs, int chunk_id, const u
 int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int stripe, int* member_out,
                                   unsigned long long* offset_out);
 
+/* ---- member checksums (zlib CRC-32 on the device) --------------------- */
+/*
+ * The parity says whether a stripe is consistent, not which bytes are wrong
+ * (an XOR row names no cell; two wrong members may look like a third), and a
+ * rebuild trusts every survivor. A content checksum per member answers both.
+ * It is the CRC-32 of zlib (reflected polynomial 0xEDB88320, initial value
+ * and final XOR 0xFFFFFFFF, 0 for no bytes): what the reference computes in
+ * redset_crc32 (src/redset_io.c:477-510) and never stored (the crc_on_copy
+ * blocks, src/redset_reedsolomon.c:557-563, :1018-1050). Computed where the
+ * cells already are; redset_amd/setfiles.py keeps it beside the set.
+ */
+
+/* zlib's crc32_combine: CRC of A||B from crc(A), crc(B), len(B). Host only. */
+unsigned redset_hip_crc32_combine(unsigned crc_a, unsigned crc_b, unsigned long long len_b);
+
+typedef struct {
+  const unsigned char* ptr;  /* device memory; any byte address */
+  size_t len;                /* any length; 0 gives CRC 0 (ptr may then be NULL) */
+} redset_hip_crc_range;
+
+/* One CRC per range; arrays copied, buffers must outlive the plan. Executes
+ * through redset_hip_plan_execute like any plan (launches only, capture-safe:
+ * no allocation, no host synchronisation, and no block waits on another, so
+ * neither the ring nor the hang count can move); every execute recomputes
+ * from the bytes then in memory. Ranges may overlap. 16-B aligned interiors
+ * take the vector path, heads and tails the byte path. Plan info: kind 7,
+ * jobs = nranges, bytes_read = the ranges' lengths summed, bytes_written 0.
+ * One plan must not execute on two streams at once (its scratch is its own). */
+int redset_hip_plan_crc32(const redset_hip_crc_range* ranges, int nranges, redset_hip_plan** out);
+/* The CRCs of the last execute (ncrcs at least the plan's ranges); ordered on
+ * `stream` after the work already there, waits for it. */
+int redset_hip_plan_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs);
+
 /* ---- stripe primitives (one stripe, device pointers) ----------------- */
 
 /* out[j] = (out[j] ^) sum_i coeffs[j*nin + i] * in[i] over GF(2^8), for
@@ -297,6 +331,26 @@ int redset_hip_rs_verify_stream(const redset_hip_rs* rs, size_t chunk_size, int 
 int redset_hip_xor_verify_stream(int ranks, size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
                                  int io_threads, const redset_hip_io* io, redset_hip_stream_stats* stats,
                                  redset_hip_verify_row* rows, int nrows);
+
+/* CRC-32 of byte spans of a host-resident set, in the members' own
+ * coordinates: the same read -> H2D -> kernel pipeline with the CRC kernels,
+ * no D2H of cells and no write stage (io->write is never called, it may be
+ * NULL; page-locked cells, io->map, are copied to the device from where they
+ * lie, with no read and no staging copy). A span is cut at cell
+ * boundaries (cell index = offset / chunk_size) and at slice boundaries
+ * within the cell, the pieces' CRCs are computed on the device and joined on
+ * the host with redset_hip_crc32_combine. Spans may be empty (CRC 0), overlap
+ * and cross any number of cells; a DATA span reaching past the member's last
+ * file reads the logical file's zero padding, as every cell read does. */
+typedef struct {
+  int rank, kind;              /* REDSET_HIP_CELL_DATA: bytes of the member's logical file;
+                                  REDSET_HIP_CELL_PARITY: bytes of its redundancy payload (after the header) */
+  unsigned long long offset;   /* first byte, in that coordinate */
+  unsigned long long len;
+} redset_hip_crc_span;
+int redset_hip_crc32_stream(size_t chunk_size, const redset_hip_crc_span* spans, int nspans, size_t slice_bytes,
+                            int io_threads, const redset_hip_io* io, redset_hip_stream_stats* stats,
+                            unsigned* crcs /* nspans */);
 
 /* The streaming calls keep a successful call's three streams and (up to
  * 256 MiB pinned, 1 GiB of device memory) its staging buffers for the next

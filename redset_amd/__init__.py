@@ -23,6 +23,7 @@ from .codec import (  # noqa: F401
     xor_plan_rebuild,
     xor_plan_verify,
 )
+from .checksum import Crc32Plan, crc32_combine  # noqa: F401
 from .setfiles import verify_set  # noqa: F401
 from .stream import rs_verify_stream, xor_verify_stream  # noqa: F401
 

@@ -25,6 +25,7 @@ PLAN_XOR_ENCODE = 3
 PLAN_XOR_REBUILD = 4
 PLAN_RS_VERIFY = 5
 PLAN_XOR_VERIFY = 6
+PLAN_CRC32 = 7
 
 # every symbol include/redset_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -85,6 +86,10 @@ EXPORTED_SYMBOLS = (
     "redset_hip_plan_verify_locate",
     "redset_hip_rs_verify_stream",
     "redset_hip_xor_verify_stream",
+    "redset_hip_crc32_combine",
+    "redset_hip_plan_crc32",
+    "redset_hip_plan_crc32_report",
+    "redset_hip_crc32_stream",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -129,6 +134,18 @@ class VerifyRow(ctypes.Structure):
     """redset_hip_verify_row: one (stripe, parity row) of a verify report."""
 
     _fields_ = [("mismatch_bytes", c_ulonglong), ("first_offset", c_ulonglong)]
+
+
+class CrcRange(ctypes.Structure):
+    """redset_hip_crc_range: bytes [ptr, ptr + len) of device memory."""
+
+    _fields_ = [("ptr", c_void_p), ("len", c_size_t)]
+
+
+class CrcSpan(ctypes.Structure):
+    """redset_hip_crc_span: bytes of a member's logical file or redundancy payload."""
+
+    _fields_ = [("rank", c_int), ("kind", c_int), ("offset", c_ulonglong), ("len", c_ulonglong)]
 
 
 class StreamIO(ctypes.Structure):
@@ -326,6 +343,11 @@ _SIGNATURES = {
         c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, _STP, POINTER(VerifyRow), c_int]),
     "redset_hip_xor_verify_stream": (
         c_int, [c_int, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, _STP, POINTER(VerifyRow), c_int]),
+    "redset_hip_crc32_combine": (c_uint, [c_uint, c_uint, c_ulonglong]),
+    "redset_hip_plan_crc32": (c_int, [POINTER(CrcRange), c_int, POINTER(c_void_p)]),
+    "redset_hip_plan_crc32_report": (c_int, [c_void_p, c_void_p, POINTER(c_uint), c_int]),
+    "redset_hip_crc32_stream": (
+        c_int, [c_size_t, POINTER(CrcSpan), c_int, c_size_t, c_int, _IOP, _STP, POINTER(c_uint)]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "codec_kernels.h"
+#include "crc32.h"
 #include "gf256.h"
 #include "stripe_map.h"
 
@@ -61,6 +62,10 @@ struct redset_hip_plan {
   uint8_t* d_scratch = nullptr;
   std::vector<uint8_t> mat;             // RS: the encoding matrix
   std::vector<const uint8_t*> cells;    // [stripe * p + member]: that member's cell of the stripe
+  // CRC plans (REDSET_HIP_PLAN_CRC32): the launch over the plan's device
+  // tables (ranges, tile numbering, one remainder per tile, the CRCs)
+  redset_hip::CrcLaunch crc{};
+  void* d_crc = nullptr;
 };
 
 namespace {
@@ -1042,6 +1047,79 @@ int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int
   return redset_hip_rs_locate_syndrome(&rs, stripe, syn.data(), member_out);
 }
 
+unsigned redset_hip_crc32_combine(unsigned crc_a, unsigned crc_b, unsigned long long len_b) {
+  // the initial and final XORs of the two CRCs cancel: crc(A||B) = crc(A) * x^(8 len B) + crc(B)
+  return redset_hip::crc_mulmod(crc_a, redset_hip::crc_xpow8(len_b)) ^ crc_b;
+}
+
+int redset_hip_plan_crc32(const redset_hip_crc_range* ranges, int nranges, redset_hip_plan** out) {
+  if (!out) return fail("plan_crc32: null plan out-pointer");
+  *out = nullptr;
+  if (!ranges) return fail("plan_crc32: null range array");
+  if (nranges <= 0) return fail("plan_crc32: %d ranges", nranges);
+  unsigned long long total = 0, tiles = 0;
+  for (int r = 0; r < nranges; ++r) {
+    if (!ranges[r].ptr && ranges[r].len > 0) return fail("plan_crc32: range %d: null pointer with %zu bytes", r, ranges[r].len);
+    total += ranges[r].len;
+    tiles += redset_hip::crc_tiles(ranges[r].ptr, ranges[r].len);
+  }
+  if (tiles > 0x7fffffffull) return fail("plan_crc32: %llu bytes are more than one plan takes", total);
+  // one device block: ranges, tile numbering, remainders, CRCs (each 16-B aligned)
+  std::vector<redset_hip::CrcRange> hr(static_cast<size_t>(nranges));
+  std::vector<int> base(static_cast<size_t>(nranges) + 1, 0);
+  for (int r = 0; r < nranges; ++r) {
+    hr[r] = redset_hip::crc_range(ranges[r].ptr, ranges[r].len);
+    base[r + 1] = base[r] + static_cast<int>(redset_hip::crc_tiles(ranges[r].ptr, ranges[r].len));
+  }
+  auto up16 = [](size_t n) { return (n + 15) & ~size_t(15); };
+  const size_t o_base = up16(hr.size() * sizeof(redset_hip::CrcRange));
+  const size_t o_rem = o_base + up16(base.size() * sizeof(int));
+  const size_t o_crc = o_rem + up16(static_cast<size_t>(tiles) * sizeof(unsigned));
+  const size_t bytes = o_crc + up16(static_cast<size_t>(nranges) * sizeof(unsigned));
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = REDSET_HIP_PLAN_CRC32;
+  plan->info.jobs = nranges;
+  plan->info.launches = tiles > 0 ? 2 : 1;
+  plan->info.bytes_read = total;
+  int rc = hip_check(hipMalloc(&plan->d_crc, bytes), "hipMalloc(crc plan)");
+  char* d = static_cast<char*>(plan->d_crc);
+  rc = rc ? rc : hip_check(hipMemset(d, 0, bytes), "hipMemset(crc plan)");
+  rc = rc ? rc : hip_check(hipMemcpy(d, hr.data(), hr.size() * sizeof(redset_hip::CrcRange), hipMemcpyHostToDevice),
+                           "hipMemcpy(crc ranges)");
+  rc = rc ? rc : hip_check(hipMemcpy(d + o_base, base.data(), base.size() * sizeof(int), hipMemcpyHostToDevice),
+                           "hipMemcpy(crc tiles)");
+  const unsigned* tables = rc ? nullptr : redset_hip::crc_device_tables();
+  if (!rc && !tables) rc = fail("plan_crc32: cannot place the lookup tables on the device");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  plan->crc.ranges = reinterpret_cast<const redset_hip::CrcRange*>(d);
+  plan->crc.tile_base = reinterpret_cast<const int*>(d + o_base);
+  plan->crc.nranges = nranges;
+  plan->crc.tile0 = 0;
+  plan->crc.ntiles = static_cast<int>(tiles);
+  plan->crc.rem = reinterpret_cast<unsigned*>(d + o_rem);
+  plan->crc.crcs = reinterpret_cast<unsigned*>(d + o_crc);
+  plan->crc.tables = tables;
+  plan->crc.xtile = redset_hip::crc_xpow8(redset_hip::kCrcTile);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs) {
+  if (!plan || !crcs) return fail("crc32_report: null argument");
+  if (plan->info.kind != REDSET_HIP_PLAN_CRC32) return fail("crc32_report: not a CRC plan (kind %d)", plan->info.kind);
+  if (ncrcs < plan->crc.nranges) return fail("crc32_report: room for %d CRCs, the plan reports %d", ncrcs, plan->crc.nranges);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = hip_check(hipMemcpyAsync(crcs, plan->crc.crcs, static_cast<size_t>(plan->crc.nranges) * sizeof(unsigned),
+                                        hipMemcpyDeviceToHost, s),
+                         "crc32 report copy"))
+    return rc;
+  return hip_check(hipStreamSynchronize(s), "crc32 report sync");
+}
+
 int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   if (!plan) return fail("null plan");
   for (const auto& C : plan->gf_checks)
@@ -1055,6 +1133,8 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
                                                plan->d_report, plan->report_rows, w.row0, plan->d_scratch, stream))
       return rc;
   }
+  if (plan->info.kind == REDSET_HIP_PLAN_CRC32)
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_crc32(plan->crc, stream)), "crc32 launch");
   for (const GfLaunch& G : plan->gf_launches)
     if (int e = redset_hip::launch_gf(G, stream)) return hip_check(static_cast<hipError_t>(e), "gf_mac launch");
   for (const XorLaunch& X : plan->xor_launches)
@@ -1075,6 +1155,7 @@ void redset_hip_plan_destroy(redset_hip_plan* plan) {
   if (plan->d_claim) (void) hipFree(plan->d_claim);
   if (plan->d_report) (void) hipFree(plan->d_report);
   if (plan->d_scratch) (void) hipFree(plan->d_scratch);
+  if (plan->d_crc) (void) hipFree(plan->d_crc);
   delete plan;
 }
 

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "codec_kernels.h"
+#include "crc32.h"
 #include "redset_hip.h"
 #include "stripe_map.h"
 
@@ -803,6 +804,275 @@ int run_verify(const std::vector<StripeMap>& maps, int e, size_t chunk, size_t s
   return REDSET_SUCCESS;
 }
 
+// CRC-32 of spans of a host-resident set (include/redset_hip.h
+// redset_hip_crc32_stream): run_verify's read -> H2D -> kernel stages with the
+// CRC kernels (crc32.h). The spans are cut into pieces that stay inside one
+// cell and one slice; consecutive pieces are packed, 256 B apart, into units
+// of one slot buffer each, and a unit is one pair of CRC launches over its
+// pieces. Every piece's device address is known before the first read (unit u
+// uses slot u % kSlots), so the range table of the whole call is uploaded
+// once and a launch takes its part of it. Page-locked pieces (io->map) are
+// copied to the device from where they lie, with no read and no staging copy.
+struct CrcPiece {
+  int span, rank, kind, index;
+  size_t off, len;
+  size_t at;  // staged: offset in its unit's slot buffer
+  int unit;
+};
+
+int run_crc_stream(size_t chunk, const redset_hip_crc_span* spans, int nspans, size_t slice, int io_threads,
+                   const redset_hip_io* io, redset_hip_stream_stats* stats, unsigned* crcs) {
+  if (nspans < 0 || (nspans > 0 && (!spans || !crcs))) return fail("crc32_stream: bad span list (%d spans)", nspans);
+  if (!io || !io->read) return fail("null redset_hip_io");
+  if (chunk == 0) return fail("crc32_stream: chunk_size 0");
+  for (int k = 0; k < nspans; ++k) {
+    const redset_hip_crc_span& S = spans[k];
+    if (S.rank < 0 || (S.kind != REDSET_HIP_CELL_DATA && S.kind != REDSET_HIP_CELL_PARITY))
+      return fail("crc32_stream: span %d: rank %d, kind %d", k, S.rank, S.kind);
+    if (S.offset + S.len < S.offset || (S.offset + S.len) / chunk > 0x7fffffffull)
+      return fail("crc32_stream: span %d: bytes [%llu, +%llu) out of range", k, S.offset, S.len);
+  }
+  redset_hip_stream_stats st;
+  std::memset(&st, 0, sizeof(st));
+  for (int k = 0; k < nspans; ++k) crcs[k] = 0;
+  if (slice == 0) slice = chunk > (8u << 20) ? (8u << 20) : std::max<size_t>(256u << 10, chunk / 16);
+  slice = std::min(slice, chunk);
+  slice = (slice + 255) & ~static_cast<size_t>(255);
+  if (io_threads <= 0) io_threads = 8;
+  const double t0 = now_s();
+
+  std::vector<CrcPiece> pieces;
+  for (int k = 0; k < nspans; ++k) {
+    unsigned long long pos = spans[k].offset, left = spans[k].len;
+    while (left > 0) {
+      const size_t off = static_cast<size_t>(pos % chunk);
+      const size_t n = static_cast<size_t>(std::min<unsigned long long>({left, chunk - off, slice - off % slice}));
+      pieces.push_back(CrcPiece{k, spans[k].rank, spans[k].kind, static_cast<int>(pos / chunk), off, n, 0, 0});
+      pos += n;
+      left -= n;
+    }
+  }
+  if (pieces.empty()) {
+    if (stats) *stats = st;
+    return REDSET_SUCCESS;
+  }
+  const size_t np = pieces.size();
+
+  // page-locked pieces (io->map, contiguous over the piece) are copied to
+  // the device straight from where they are; the others are read into the
+  // slot's pinned buffer first
+  bool use_map = io->map != nullptr;
+#if REDSET_HIP_TEST_KNOBS
+  {
+    const char* env = std::getenv("REDSET_HIP_ZERO_COPY");
+    if (env && env[0] == '0') use_map = false;
+  }
+#endif
+  std::vector<const void*> src(np, nullptr);
+  for (size_t i = 0; i < np && use_map; ++i) {
+    const CrcPiece& P = pieces[i];
+    void* h0 = io->map(io->ctx, P.rank, P.kind, P.index, P.off);
+    void* h1 = io->map(io->ctx, P.rank, P.kind, P.index, P.off + P.len - 1);
+    if (h0 && static_cast<char*>(h1) == static_cast<char*>(h0) + (P.len - 1)) src[i] = h0;
+  }
+  std::vector<const uint8_t*> where(np, nullptr);  // device address of every piece
+  // staged: units of up to `cap` bytes of pieces, 256 B apart
+  const size_t cap = std::max(slice, std::min<size_t>(size_t(32) << 20, 16 * slice));
+  std::vector<size_t> unit_first;  // first piece of every unit, then np
+  {
+    size_t used = cap;
+    for (size_t i = 0; i < np; ++i) {
+      size_t at = (used + 255) & ~static_cast<size_t>(255);
+      if (at + pieces[i].len > cap) {
+        unit_first.push_back(i);
+        at = 0;
+      }
+      pieces[i].at = at;
+      pieces[i].unit = static_cast<int>(unit_first.size()) - 1;
+      used = at + pieces[i].len;
+    }
+  }
+  unit_first.push_back(np);
+  const size_t nunits = unit_first.size() - 1;
+
+  Slot slots[kSlots];
+  ResourceCache& cache = ResourceCache::get();
+  hipStream_t s_in = cache.take_stream(), s_comp = cache.take_stream();
+  int rc = (s_in && s_comp) ? 0 : fail("hipStreamCreate failed");
+  auto buf = [&](uint8_t** p, size_t* have, size_t n, bool on_dev) {
+    if (rc) return;
+    *p = static_cast<uint8_t*>(cache.take_buf(n, on_dev, have));
+    if (!*p) rc = fail("%s(%zu) failed", on_dev ? "hipMalloc" : "hipHostMalloc", n);
+  };
+  for (size_t k = 0; k < std::min<size_t>(kSlots, nunits); ++k) {
+      Slot& S = slots[k];
+      buf(&S.h_in, &S.n_h_in, cap, false);
+      buf(&S.d_in, &S.n_d_in, cap, true);
+      rc = rc ? rc : hip_ok(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming), "event");
+      rc = rc ? rc : hip_ok(hipEventCreate(&S.ev_start), "event");
+      rc = rc ? rc : hip_ok(hipEventCreate(&S.ev_done), "event");
+    }
+  // the call's device tables: ranges, tile numbering, remainders, piece CRCs
+  std::vector<redset_hip::CrcRange> hr(np);
+  std::vector<int> base(np + 1, 0);
+  unsigned long long tiles = 0;
+  for (size_t i = 0; i < np && rc == 0; ++i) {
+    where[i] = slots[pieces[i].unit % kSlots].d_in + pieces[i].at;
+    hr[i] = redset_hip::crc_range(where[i], pieces[i].len);
+    tiles += redset_hip::crc_tiles(where[i], pieces[i].len);
+    if (tiles > 0x7fffffffull) rc = fail("crc32_stream: too many bytes for one call");
+    base[i + 1] = static_cast<int>(tiles);
+  }
+  auto up16 = [](size_t n) { return (n + 15) & ~size_t(15); };
+  const size_t o_base = up16(np * sizeof(redset_hip::CrcRange));
+  const size_t o_rem = o_base + up16((np + 1) * sizeof(int));
+  const size_t o_crc = o_rem + up16(static_cast<size_t>(tiles) * sizeof(unsigned));
+  uint8_t* d_tab = nullptr;
+  size_t n_tab = 0;
+  buf(&d_tab, &n_tab, o_crc + up16(np * sizeof(unsigned)), true);
+  rc = rc ? rc : hip_ok(hipMemcpy(d_tab, hr.data(), np * sizeof(redset_hip::CrcRange), hipMemcpyHostToDevice), "crc ranges copy");
+  rc = rc ? rc : hip_ok(hipMemcpy(d_tab + o_base, base.data(), (np + 1) * sizeof(int), hipMemcpyHostToDevice), "crc tiles copy");
+  redset_hip::CrcLaunch all{};
+  if (rc == 0) {
+    all.ranges = reinterpret_cast<const redset_hip::CrcRange*>(d_tab);
+    all.tile_base = reinterpret_cast<const int*>(d_tab + o_base);
+    all.rem = reinterpret_cast<unsigned*>(d_tab + o_rem);
+    all.crcs = reinterpret_cast<unsigned*>(d_tab + o_crc);
+    all.tables = redset_hip::crc_device_tables();
+    all.xtile = redset_hip::crc_xpow8(redset_hip::kCrcTile);
+    if (!all.tables) rc = fail("crc32_stream: cannot place the lookup tables on the device");
+  }
+  // the launch over pieces [a, b)
+  auto launch = [&](size_t a, size_t b) {
+    redset_hip::CrcLaunch L = all;
+    L.ranges += a;
+    L.tile_base += a;
+    L.crcs += a;
+    L.nranges = static_cast<int>(b - a);
+    L.tile0 = base[a];
+    L.ntiles = base[b] - base[a];
+    return hip_ok(static_cast<hipError_t>(redset_hip::launch_crc32(L, s_comp)), "crc32 launch");
+  };
+
+  std::atomic<int> io_err(0);
+  std::atomic<long long> read_ns(0);
+  double gpu_s = 0;
+  if (rc == 0) {
+    std::mutex mu;
+    std::condition_variable cv;
+    IoPool rpool(io_threads);
+    std::atomic<bool> abort(false);
+    auto wait_state = [&](Slot& S, SlotState w) {
+      std::unique_lock<std::mutex> lk(mu);
+      cv.wait(lk, [&] { return S.state == w || abort.load(); });
+      return !abort.load();
+    };
+    auto stop = [&] {
+      {
+        std::lock_guard<std::mutex> g(mu);
+        abort = true;
+      }
+      cv.notify_all();
+    };
+    auto set_state = [&](Slot& S, SlotState v) {
+      {
+        std::lock_guard<std::mutex> g(mu);
+        S.state = v;
+      }
+      cv.notify_all();
+    };
+    std::thread reader([&] {
+      for (size_t u = 0; u < nunits; ++u) {
+        Slot& S = slots[u % kSlots];
+        if (!wait_state(S, kFree)) return;
+        std::vector<std::function<void()>> tasks;
+        for (size_t i = unit_first[u]; i < unit_first[u + 1]; ++i) {
+          if (src[i]) continue;  // copied straight from mapped host memory
+          tasks.push_back([&, i] {
+            const CrcPiece& P = pieces[i];
+            const double a = now_s();
+            if (io->read(io->ctx, P.rank, P.kind, P.index, P.off, P.len, S.h_in + P.at) != 0) io_err = 1;
+            read_ns += static_cast<long long>((now_s() - a) * 1e9);
+          });
+        }
+        rpool.run(tasks);
+        S.unit = u;
+        set_state(S, kRead);
+      }
+    });
+    // frees a slot once its unit's kernels are done
+    std::thread releaser([&] {
+      for (size_t u = 0; u < nunits; ++u) {
+        Slot& S = slots[u % kSlots];
+        if (!wait_state(S, kOnGpu)) return;
+        if (hipEventSynchronize(S.ev_done) != hipSuccess) {
+          io_err = 2;
+          stop();
+          return;
+        }
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, S.ev_start, S.ev_done) == hipSuccess) gpu_s += ms * 1e-3;
+        set_state(S, kFree);
+      }
+    });
+    for (size_t u = 0; u < nunits && rc == 0; ++u) {
+      Slot& S = slots[u % kSlots];
+      if (!wait_state(S, kRead)) break;
+      const size_t a = unit_first[u], b = unit_first[u + 1];
+      const size_t used = pieces[b - 1].at + pieces[b - 1].len;
+      rc = rc ? rc : hip_ok(hipEventRecord(S.ev_start, s_in), "event record");
+      bool any_mapped = false;
+      for (size_t i = a; i < b; ++i) any_mapped = any_mapped || src[i];
+      if (!any_mapped) {
+        rc = rc ? rc : hip_ok(hipMemcpyAsync(S.d_in, S.h_in, used, hipMemcpyHostToDevice, s_in), "H2D");
+      } else {
+        for (size_t i = a; i < b && rc == 0; ++i)
+          rc = hip_ok(hipMemcpyAsync(S.d_in + pieces[i].at, src[i] ? src[i] : S.h_in + pieces[i].at, pieces[i].len,
+                                     hipMemcpyHostToDevice, s_in),
+                      "H2D");
+      }
+      rc = rc ? rc : hip_ok(hipEventRecord(S.ev_in, s_in), "event record");
+      rc = rc ? rc : hip_ok(hipStreamWaitEvent(s_comp, S.ev_in, 0), "stream wait");
+      rc = rc ? rc : launch(a, b);
+      rc = rc ? rc : hip_ok(hipEventRecord(S.ev_done, s_comp), "event record");
+      if (rc != 0) break;
+      for (size_t i = a; i < b; ++i) st.bytes_read += pieces[i].len;
+      st.units += 1;
+      set_state(S, kOnGpu);
+    }
+    if (rc != 0) stop();
+    reader.join();
+    releaser.join();
+  }
+  bool ok = rc == 0 && io_err.load() != 2;
+  for (hipStream_t s : {s_in, s_comp})
+    if (s && hipStreamSynchronize(s) != hipSuccess) ok = false;
+  if (ok && rc == 0 && io_err.load() == 0) {
+    std::vector<unsigned> got(np);
+    rc = hip_ok(hipMemcpy(got.data(), all.crcs, np * sizeof(unsigned), hipMemcpyDeviceToHost), "crc copy");
+    for (size_t i = 0; i < np && rc == 0; ++i)
+      crcs[pieces[i].span] = redset_hip_crc32_combine(crcs[pieces[i].span], got[i], pieces[i].len);
+  }
+  cache.give_buf(d_tab, n_tab, true, ok);
+  for (Slot& S : slots) {
+    cache.give_buf(S.h_in, S.n_h_in, false, ok);
+    cache.give_buf(S.d_in, S.n_d_in, true, ok);
+    if (S.ev_in) (void) hipEventDestroy(S.ev_in);
+    if (S.ev_start) (void) hipEventDestroy(S.ev_start);
+    if (S.ev_done) (void) hipEventDestroy(S.ev_done);
+  }
+  cache.give_stream(s_in, ok);
+  cache.give_stream(s_comp, ok);
+  st.seconds = now_s() - t0;
+  st.read_seconds = read_ns.load() * 1e-9;
+  st.gpu_seconds = gpu_s;
+  if (stats) *stats = st;
+  if (rc) return rc;
+  if (io_err.load() == 2) return fail("crc32 pipeline: a device wait failed");
+  if (io_err.load()) return fail("stream I/O callback failed");
+  return REDSET_SUCCESS;
+}
+
 int stripe_range(int ranks, int first, int n, int& lo, int& hi) {
   if (n <= 0) {
     first = 0;
@@ -1014,6 +1284,11 @@ int redset_hip_xor_verify_stream(int ranks, size_t chunk_size, int first_stripe,
   std::vector<StripeMap> maps(hi - lo);
   for (int c = lo; c < hi; ++c) redset_hip::xor_encode_map(ranks, c, maps[c - lo]);
   return run_verify(maps, 1, chunk_size, slice_bytes, io_threads, io, stats, rows, nrows);
+}
+
+int redset_hip_crc32_stream(size_t chunk_size, const redset_hip_crc_span* spans, int nspans, size_t slice_bytes,
+                            int io_threads, const redset_hip_io* io, redset_hip_stream_stats* stats, unsigned* crcs) {
+  return run_crc_stream(chunk_size, spans, nspans, slice_bytes, io_threads, io, stats, crcs);
 }
 
 int redset_hip_hostio_create(int ranks, unsigned char* const* lofi, unsigned char* const* parity, size_t cell_stride,

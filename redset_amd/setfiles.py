@@ -12,6 +12,7 @@ Headers: redset_amd.header (tree content pinned by the reference's documented
 examples; KVTree's byte layout unpinned)."""
 from __future__ import annotations
 
+import json
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -27,13 +28,95 @@ def _codec(scheme: str, ranks: int, encoding: int):
     return None
 
 
+SIDECAR_SUFFIX = ".crc"
+
+
+def _checksum_table(files, reds, hsize, chunk: int, k: int, slice_bytes: int = 0, members=None) -> Dict[int, Dict]:
+    """CRC-32 of every data file and of the redundancy payload (the k parity
+    chunks after the header) of the listed members (default: all), in one
+    crc32_stream pass over the files: {member: {"files": [[name, size, crc],
+    ...], "payload": crc}}. A file's span is its own bytes in the member's
+    logical file, so the zero padding after the last file is in no CRC."""
+    members = list(range(len(files))) if members is None else list(members)
+    spans, where = [], []
+    for r in members:
+        pos = 0
+        for i, (_, size) in enumerate(files[r]):
+            spans.append((r, 0, pos, size))
+            where.append((r, i))
+            pos += size
+        spans.append((r, 1, 0, k * chunk))
+        where.append((r, None))
+    io = stream.FileIO(files, reds, hsize, chunk)
+    try:
+        crcs = stream.crc32_stream(chunk, io, spans, slice_bytes=slice_bytes)["crcs"]
+    finally:
+        io.close()
+    table = {r: {"files": [[path, size, None] for path, size in files[r]], "payload": None} for r in members}
+    for (r, i), crc in zip(where, crcs):
+        if i is None:
+            table[r]["payload"] = crc
+        else:
+            table[r]["files"][i][2] = crc
+    return table
+
+
+def _write_sidecars(reds, members, scheme: str, chunk: int, k: int, table: Dict[int, Dict]) -> None:
+    """The whole set's table beside the redundancy file of every member of
+    ``members``: any loss the set survives leaves a copy, as every header
+    carries every member's descriptor."""
+    doc = {"format": 1, "checksum": "crc32", "scheme": scheme, "ranks": len(reds), "encoding": k, "chunk": chunk,
+           "members": [{"rank": r, "files": table[r]["files"], "payload": table[r]["payload"]}
+                       for r in sorted(table)]}
+    text = json.dumps(doc, indent=1, sort_keys=True) + "\n"
+    for r in members:
+        tmp = reds[r] + SIDECAR_SUFFIX + ".tmp"
+        with open(tmp, "w") as fh:
+            fh.write(text)
+        os.replace(tmp, reds[r] + SIDECAR_SUFFIX)
+
+
+def _read_sidecar(reds, p: int, chunk: int) -> Dict[int, Dict]:
+    """The table of the first readable sidecar that describes this set."""
+    for red in reds:
+        try:
+            with open(red + SIDECAR_SUFFIX) as fh:
+                doc = json.load(fh)
+            if doc["checksum"] != "crc32" or doc["ranks"] != p or doc["chunk"] != chunk:
+                continue
+            table = {int(m["rank"]): {"files": m["files"], "payload": m["payload"]} for m in doc["members"]}
+            if sorted(table) == list(range(p)):
+                return table
+        except (OSError, ValueError, KeyError, TypeError):
+            continue
+    raise ValueError("no readable checksum sidecar (" + SIDECAR_SUFFIX + ") beside any redundancy file of the set")
+
+
+def _checksum_diff(stored: Dict[int, Dict], now: Dict[int, Dict], reds) -> List[Dict]:
+    """What differs: [{"member", "kind": "data" | "parity", "file"}]."""
+    bad = []
+    for r in sorted(now):
+        for i, (path, size, crc) in enumerate(now[r]["files"]):
+            old = stored[r]["files"][i] if i < len(stored[r]["files"]) else None
+            if old is None or old[1] != size or old[2] != crc:
+                bad.append({"member": r, "kind": "data", "file": path})
+        if stored[r]["payload"] != now[r]["payload"]:
+            bad.append({"member": r, "kind": "parity", "file": reds[r]})
+    return bad
+
+
 def apply_set(scheme: str, member_files: Sequence[Sequence[str]], prefix: str, encoding: int = 1,
               world_ranks: Optional[Sequence[int]] = None, world_size: Optional[int] = None,
-              group_id: int = 0, groups: int = 1, slice_bytes: int = 0) -> Dict:
+              group_id: int = 0, groups: int = 1, slice_bytes: int = 0, checksums: bool = False) -> Dict:
     """Encode a set whose members' data files are ``member_files[r]``: write
     member r's redundancy file ``redundancy_filename(prefix, ...)`` with its
     header and its parity chunks. Returns the file names, CHUNK and the
-    pipeline statistics."""
+    pipeline statistics. ``checksums``: also write, beside every redundancy
+    file, a sidecar ``<redundancy file>.crc`` with the CRC-32 of every
+    member's data files and redundancy payload (one more pass over the set,
+    on the GPU; the redundancy files themselves are unchanged), for
+    verify_set / rebuild_set(checksums=True); the result gains
+    ``"checksums"``."""
     scheme = scheme.upper()
     if scheme not in ("RS", "XOR"):
         raise ValueError(f"unknown scheme {scheme!r}")
@@ -62,7 +145,12 @@ def apply_set(scheme: str, member_files: Sequence[Sequence[str]], prefix: str, e
             st = stream.xor_encode_stream(p, chunk, io, slice_bytes=slice_bytes)
     finally:
         io.close()
-    return {"redundancy": reds, "chunk": chunk, "header_bytes": hsize, "stats": st}
+    out = {"redundancy": reds, "chunk": chunk, "header_bytes": hsize, "stats": st}
+    if checksums:
+        files = [[(m.path, m.size) for m in ms] for ms in metas]
+        out["checksums"] = _checksum_table(files, reds, hsize, chunk, k, slice_bytes)
+        _write_sidecars(reds, range(p), scheme, chunk, k, out["checksums"])
+    return out
 
 
 def _files_ok(files) -> bool:
@@ -137,7 +225,7 @@ def _read_set(redundancy_files: Sequence[str]):
     return f, reds, files, lost
 
 
-def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
+def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums: bool = False) -> Dict:
     """Rebuild the lost members of one set from the redundancy files that can
     still be read (``redundancy_files`` may name lost ones too). A member is
     lost when its redundancy file is unreadable or shorter than header + k
@@ -145,7 +233,12 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
     members than the scheme tolerates is an error
     (src/redset_reedsolomon_serial.c:496-519). Lost members get
     their data files, file metadata and redundancy file (header regenerated
-    from the set facts, so it matches what apply_set wrote) back."""
+    from the set facts, so it matches what apply_set wrote) back.
+    ``checksums``: with a surviving checksum sidecar (apply_set(checksums=
+    True)), every rebuilt data file and redundancy payload is checked against
+    it after the rebuild -- a silently damaged survivor gives a wrong rebuild,
+    reported in ``errors`` (``ok`` false) -- and the lost members' sidecars
+    are written again. No sidecar: a ValueError before anything is written."""
     f, reds, files, lost = _read_set(redundancy_files)
     p, k = f.ranks, f.encoding
     out = {"scheme": f.scheme, "ranks": p, "encoding": k, "chunk": f.chunk, "missing": lost,
@@ -154,6 +247,7 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
         return out
     if len(lost) > k:
         raise ValueError(f"{len(lost)} members lost but {f.scheme} tolerates {k}")
+    stored = _read_sidecar(reds, p, f.chunk) if checksums else None
     hsize = [f.header_size.get(r, 0) for r in range(p)]
     for r in lost:
         for path, _ in files[r]:
@@ -178,6 +272,13 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
         for i, (path, _) in enumerate(files[r]):
             (_, meta), = f.members[r]["FILE"][str(i)].items()
             out["errors"] += _apply_meta(path, meta)
+    if stored is not None:
+        now = _checksum_table(files, reds, hsize, f.chunk, k, slice_bytes, members=lost)
+        out["checksum_damaged"] = _checksum_diff(stored, now, reds)
+        for d in out["checksum_damaged"]:
+            out["errors"].append(f"{d['file']}: rebuilt {d['kind']} of member {d['member']} does not match its "
+                                 "recorded CRC-32 (a surviving member is damaged)")
+        _write_sidecars(reds, lost, f.scheme, f.chunk, k, stored)
     out["ok"] = not out["errors"]
     return out
 
@@ -212,7 +313,20 @@ def _cell_byte(files, red: str, header: int, chunk: int, kind_data: bool, index:
     return 0
 
 
-def verify_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
+def _cell_range(scheme: str, codec, p: int, member: int, stripe: int, chunk: int):
+    """Member's cell of a stripe: ("data", first byte in its logical file) or
+    ("parity", first byte in its redundancy payload)."""
+    if scheme == "RS":
+        enc = codec.encoding_id(member, stripe)
+        if enc < p:
+            return "data", codec.data_id(member, stripe) * chunk
+        return "parity", (enc - p) * chunk
+    if member == stripe:
+        return "parity", 0
+    return "data", (stripe if stripe < member else stripe - 1) * chunk
+
+
+def verify_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums: bool = False) -> Dict:
     """Scrub one set on disk: stream every member's data files and parity
     chunks through the check kernels (redset_amd.stream.*_verify_stream;
     nothing is written) and report whether the stored parity still matches
@@ -223,7 +337,16 @@ def verify_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
     differing cell ``offset``, the located ``member`` (None for XOR sets or
     when no single member explains the column) and whether that member's
     wrong cell is ``"data"`` or ``"parity"``. A located member is repaired by
-    removing its files and calling rebuild_set."""
+    removing its files and calling rebuild_set.
+    ``checksums``: also recompute every member's CRC-32s (one crc32_stream
+    pass) and compare them with the set's checksum sidecar (apply_set(
+    checksums=True); none readable: ValueError). ``checksum_damaged`` lists
+    what differs as {"member", "kind": "data" | "parity", "file"}; any entry
+    makes ``clean`` false. A damaged stripe whose ``member`` the syndrome
+    cannot name (XOR sets; columns no single member explains) takes it from
+    there when exactly one member's differing file covers its cell of that
+    stripe; where the syndrome did name one, ``member`` stays the syndrome's
+    answer and the CRC's stands beside it."""
     f, reds, files, lost = _read_set(redundancy_files)
     p, k = f.ranks, f.encoding
     if lost:
@@ -262,4 +385,28 @@ def verify_set(redundancy_files: Sequence[str], slice_bytes: int = 0) -> Dict:
                 entry["member"] = m
                 entry["kind"] = "data" if codec.encoding_id(m, c) < p else "parity"
         out["damaged"].append(entry)
+    if checksums:
+        stored = _read_sidecar(reds, p, f.chunk)
+        now = _checksum_table(files, reds, hsize, f.chunk, k, slice_bytes)
+        bad = _checksum_diff(stored, now, reds)
+        out["checksum_damaged"] = bad
+        out["clean"] = out["clean"] and not bad
+        for entry in out["damaged"]:
+            if entry["member"] is not None:
+                continue
+            hits = set()
+            for d in bad:
+                kind, lo = _cell_range(f.scheme, codec, p, d["member"], entry["stripe"], f.chunk)
+                if kind != d["kind"]:
+                    continue
+                if kind == "data":  # the file's bytes in the logical file against the cell's
+                    pos = 0
+                    for path, size in files[d["member"]]:
+                        if path == d["file"] and pos < lo + f.chunk and pos + size > lo:
+                            hits.add((d["member"], kind))
+                        pos += size
+                else:
+                    hits.add((d["member"], kind))
+            if len(hits) == 1:
+                (entry["member"], entry["kind"]), = hits
     return out

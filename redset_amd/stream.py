@@ -121,6 +121,25 @@ def xor_verify_stream(ranks: int, chunk: int, io, first: int = 0, nstripes: int 
                    io_threads, ctypes.byref(io.io))
 
 
+def crc32_stream(chunk: int, io, spans: Sequence[Tuple[int, int, int, int]], slice_bytes: int = 0,
+                 io_threads: int = 0) -> dict:
+    """zlib CRC-32 of every span ``(rank, kind, offset, length)`` of a
+    host-resident set -- kind 0: bytes of the member's logical file, 1: bytes
+    of its redundancy payload -- computed on the GPU (include/redset_hip.h
+    redset_hip_crc32_stream). Reads only. Returns ``crcs`` and the pipeline
+    statistics."""
+    from ctypes import c_uint
+
+    arr = (_lib.CrcSpan * max(1, len(spans)))()
+    for i, (rank, kind, off, n) in enumerate(spans):
+        arr[i] = _lib.CrcSpan(int(rank), int(kind), int(off), int(n))
+    out = (c_uint * max(1, len(spans)))()
+    st = _lib.StreamStats()
+    _lib.check(_lib.load().redset_hip_crc32_stream(chunk, arr, len(spans), slice_bytes, io_threads,
+                                                   ctypes.byref(io.io), ctypes.byref(st), out), "crc32_stream")
+    return {"crcs": [int(x) for x in out[:len(spans)]], "stats": st.as_dict()}
+
+
 def chunk_size_for(max_bytes: int, data_cells: int) -> int:
     """redset_apply_rs / redset_apply_xor chunk size: ceil(max / data cells),
     at least 1 (src/redset_reedsolomon.c:485-493, src/redset_xor.c:362-370)."""
