@@ -50,7 +50,8 @@ enum {
   REDSET_HIP_PLAN_XOR_REBUILD = 4,
   REDSET_HIP_PLAN_RS_VERIFY = 5,
   REDSET_HIP_PLAN_XOR_VERIFY = 6,
-  REDSET_HIP_PLAN_CRC32 = 7
+  REDSET_HIP_PLAN_CRC32 = 7,
+  REDSET_HIP_PLAN_RS_REPAIR = 8
 };
 
 typedef struct {
@@ -192,6 +193,53 @@ int redset_hip_rs_locate_syndrome(const redset_hip_rs* rs, int chunk_id, const u
 int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int stripe, int* member_out,
                                   unsigned long long* offset_out);
 
+/* ---- repair (single-error-per-column correction) ---------------------- */
+/*
+ * What follows a scrub that found damage, short of a rebuild: for every byte
+ * column of a damaged stripe, form the syndrome, apply exactly the rule of
+ * redset_hip_rs_locate_syndrome and XOR the one wrong byte right. Only the
+ * wrong bytes are written. Members each damaged at different offsets -- more
+ * members than a rebuild has erasures for -- are repaired as long as every
+ * byte column has at most one wrong byte. RS sets with 2 <= e <= 4 only: one
+ * parity row (e = 1, XOR sets) locates nothing, and e > 4 is not built.
+ * Capability per e: a column with one wrong byte is always corrected; a
+ * column with two wrong bytes is reported unlocated for e >= 3 and, for
+ * e == 2 (distance 3), may be reported unlocated or MIScorrected into a third
+ * member -- the member checksums below arbitrate (setfiles.repair_set
+ * checksums=True). Columns no single member explains are left as found.
+ */
+typedef struct {
+  unsigned long long corrected_bytes;  /* bytes of this member's cell of this stripe that were (apply) or would be (dry run) corrected */
+  unsigned long long first_offset;     /* smallest such cell offset; ~0ULL if none */
+} redset_hip_repair_cell;              /* [stripe * p + member] */
+typedef struct {
+  unsigned long long unlocated_columns; /* nonzero-syndrome byte columns no single member explains */
+  unsigned long long first_unlocated;   /* ~0ULL if none */
+} redset_hip_repair_stripe;             /* [stripe] */
+
+/* Repair plan over `nstripes` stripes (stripes[k] in 0 .. p-1, each at most
+ * once; NULL: all p, in order). apply == 0 is a dry run: the same report, no
+ * cell byte written. Executes through redset_hip_plan_execute like any plan:
+ * kernel launches only (the report is reset by one), no allocation, no host
+ * synchronisation (safe inside hipStreamBeginCapture), no block waits on
+ * another, so neither the ring nor the hang count can move. 16-B aligned
+ * stripes take the vector path, stripes with an unaligned cell and tails the
+ * byte path. Plan info: kind 8, jobs = stripes planned, bytes_read =
+ * stripes * (d + e) * chunk_size, bytes_written = 0: the corrections are
+ * data-dependent (one byte read again and written per corrected byte) and
+ * not counted. One plan must not execute on two streams at once. */
+int redset_hip_rs_plan_repair(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                              size_t chunk_size, size_t cell_stride, int nstripes, const int* stripes /* NULL: all p */,
+                              int apply, redset_hip_plan** out);
+/* The report of the plan's last execute, for the planned stripes in plan
+ * order: cells[k * p + member] (ncells at least planned stripes * p) and
+ * stripes[k] (nstripes at least the planned stripes); either may be NULL.
+ * Ordered on `stream` after the work already there; waits for it. */
+int redset_hip_plan_repair_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells, int ncells,
+                                  redset_hip_repair_stripe* stripes, int nstripes);
+
+typedef struct { unsigned long long verify_mismatch_bytes, corrected_bytes, unlocated_columns,
+                 remaining_mismatch_bytes; int damaged_stripes, repair_units, cells_written; } redset_hip_repair_summary;
 /* ---- member checksums (zlib CRC-32 on the device) --------------------- */
 /*
  * The parity says whether a stripe is consistent, not which bytes are wrong
@@ -331,6 +379,29 @@ int redset_hip_rs_verify_stream(const redset_hip_rs* rs, size_t chunk_size, int 
 int redset_hip_xor_verify_stream(int ranks, size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
                                  int io_threads, const redset_hip_io* io, redset_hip_stream_stats* stats,
                                  redset_hip_verify_row* rows, int nrows);
+
+/* Repair a host-resident set (memory or files, see "repair" above):
+ * 1. redset_hip_rs_verify_stream over the stripes; a clean result returns at
+ *    once (repair_units == 0, no repair launch): a clean scrub costs what it
+ *    costs today.
+ * 2. every stripe with a nonzero row, slice by slice, synchronously: io->read
+ *    the stripe's p cell slices, run the repair kernel on them, read the
+ *    slice's report (offsets are cell offsets) and, with apply, io->write
+ *    only the cells corrected in that slice, only that slice's range
+ *    (cells_written counts them; repair_units the slices).
+ * 3. with apply, the check kernels again over the repaired stripes:
+ *    remaining_mismatch_bytes (a correction that falls into a logical file's
+ *    zero padding is dropped by the file I/O's write rule and shows here);
+ *    without, remaining_mismatch_bytes == verify_mismatch_bytes.
+ * cells[(stripe - first_stripe) * p + member] and stripes[stripe -
+ * first_stripe] are summed over the slices (each may be NULL). Returns
+ * REDSET_SUCCESS when the procedure RAN (damage is in the outputs),
+ * REDSET_FAILURE on I/O or device errors. io->write may be NULL when
+ * apply == 0. Device and pinned memory are allocated per call. */
+int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
+                                redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
+                                redset_hip_repair_stripe* stripes, int nstripes_out, redset_hip_repair_summary* summary);
 
 /* CRC-32 of byte spans of a host-resident set, in the members' own
  * coordinates: the same read -> H2D -> kernel pipeline with the CRC kernels,

@@ -12,6 +12,7 @@ from ._lib import LIB_PATH, RedsetHipError, RedsetHipUnavailable, load  # noqa: 
 from .codec import (  # noqa: F401
     Plan,
     RSCodec,
+    RepairPlan,
     SetLayout,
     VerifyPlan,
     gf_combine,
@@ -21,10 +22,11 @@ from .codec import (  # noqa: F401
     xor_combine,
     xor_plan_encode,
     xor_plan_rebuild,
+    xor_plan_repair,
     xor_plan_verify,
 )
 from .checksum import Crc32Plan, crc32_combine  # noqa: F401
-from .setfiles import verify_set  # noqa: F401
-from .stream import rs_verify_stream, xor_verify_stream  # noqa: F401
+from .setfiles import repair_set, verify_set  # noqa: F401
+from .stream import rs_repair_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
 
 __version__ = "0.1.0"

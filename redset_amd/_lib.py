@@ -26,6 +26,7 @@ PLAN_XOR_REBUILD = 4
 PLAN_RS_VERIFY = 5
 PLAN_XOR_VERIFY = 6
 PLAN_CRC32 = 7
+PLAN_RS_REPAIR = 8
 
 # every symbol include/redset_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -90,6 +91,9 @@ EXPORTED_SYMBOLS = (
     "redset_hip_plan_crc32",
     "redset_hip_plan_crc32_report",
     "redset_hip_crc32_stream",
+    "redset_hip_rs_plan_repair",
+    "redset_hip_plan_repair_report",
+    "redset_hip_rs_repair_stream",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -134,6 +138,35 @@ class VerifyRow(ctypes.Structure):
     """redset_hip_verify_row: one (stripe, parity row) of a verify report."""
 
     _fields_ = [("mismatch_bytes", c_ulonglong), ("first_offset", c_ulonglong)]
+
+
+class RepairCell(ctypes.Structure):
+    """redset_hip_repair_cell: one (stripe, member) of a repair report."""
+
+    _fields_ = [("corrected_bytes", c_ulonglong), ("first_offset", c_ulonglong)]
+
+
+class RepairStripe(ctypes.Structure):
+    """redset_hip_repair_stripe: one stripe's unlocated columns."""
+
+    _fields_ = [("unlocated_columns", c_ulonglong), ("first_unlocated", c_ulonglong)]
+
+
+class RepairSummary(ctypes.Structure):
+    """redset_hip_repair_summary: totals of one redset_hip_rs_repair_stream call."""
+
+    _fields_ = [
+        ("verify_mismatch_bytes", c_ulonglong),
+        ("corrected_bytes", c_ulonglong),
+        ("unlocated_columns", c_ulonglong),
+        ("remaining_mismatch_bytes", c_ulonglong),
+        ("damaged_stripes", c_int),
+        ("repair_units", c_int),
+        ("cells_written", c_int),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class CrcRange(ctypes.Structure):
@@ -348,6 +381,13 @@ _SIGNATURES = {
     "redset_hip_plan_crc32_report": (c_int, [c_void_p, c_void_p, POINTER(c_uint), c_int]),
     "redset_hip_crc32_stream": (
         c_int, [c_size_t, POINTER(CrcSpan), c_int, c_size_t, c_int, _IOP, _STP, POINTER(c_uint)]),
+    "redset_hip_rs_plan_repair": (
+        c_int, [c_void_p, _PP, _PP, c_size_t, c_size_t, c_int, POINTER(c_int), c_int, POINTER(c_void_p)]),
+    "redset_hip_plan_repair_report": (
+        c_int, [c_void_p, c_void_p, POINTER(RepairCell), c_int, POINTER(RepairStripe), c_int]),
+    "redset_hip_rs_repair_stream": (
+        c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, c_int, _STP, POINTER(RepairCell), c_int,
+                POINTER(RepairStripe), c_int, POINTER(RepairSummary)]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

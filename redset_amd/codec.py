@@ -129,6 +129,37 @@ class VerifyPlan(Plan):
         return int(m.value), (None if off.value == NO_OFFSET else int(off.value))
 
 
+def repair_arrays(cells, stripes, n: int, p: int):
+    """(corrected[n, p], first[n, p], unlocated[n], first_unlocated[n]) of
+    redset_hip_repair_cell / redset_hip_repair_stripe arrays."""
+    corrected = np.array([int(c.corrected_bytes) for c in cells[:n * p]], dtype=np.uint64).reshape(n, p)
+    first = np.array([int(c.first_offset) for c in cells[:n * p]], dtype=np.uint64).reshape(n, p)
+    unloc = np.array([int(s.unlocated_columns) for s in stripes[:n]], dtype=np.uint64)
+    first_unloc = np.array([int(s.first_unlocated) for s in stripes[:n]], dtype=np.uint64)
+    return corrected, first, unloc, first_unloc
+
+
+class RepairPlan(Plan):
+    """A repair plan: execute() locates, for every byte column of the planned
+    stripes, the one member whose wrong byte explains the syndrome and (made
+    with apply=True) XORs that byte right; nothing else is written
+    (include/redset_hip.h, "repair")."""
+
+    def report(self, stream=None):
+        """``(corrected, first, unlocated, first_unlocated)`` of the last
+        execute: numpy uint64 arrays [n, p] -- corrected bytes of member m's
+        cell of the k-th planned stripe and the smallest corrected cell offset
+        (NO_OFFSET if none) -- and [n] -- byte columns no single member
+        explains, and the first of them. n = the stripes planned (p when none
+        were listed). Waits for the work on ``stream``."""
+        n, p = int(self.info.jobs), int(self.info.ranks)
+        cells = (_lib.RepairCell * max(1, n * p))()
+        stripes = (_lib.RepairStripe * max(1, n))()
+        _lib.check(_lib.load().redset_hip_plan_repair_report(self._h, _stream_handle(stream), cells, n * p,
+                                                             stripes, n), "plan_repair_report")
+        return repair_arrays(cells, stripes, n, p)
+
+
 class RSCodec:
     """GF(2^8) tables + encoding matrix for a set of ``ranks`` members with
     ``encoding`` parity cells per stripe (redset_construct_rs,
@@ -203,6 +234,22 @@ class RSCodec:
         )
         return VerifyPlan(h, (self, lofi, parity))
 
+    def plan_repair(self, lofi, parity, chunk_size: int, cell_stride: Optional[int] = None,
+                    stripes: Optional[Sequence[int]] = None, apply: bool = True) -> "RepairPlan":
+        """Correct, in the listed stripes (default: all), every byte column
+        with one wrong byte; ``apply=False`` only reports. 2 <= e <= 4."""
+        stride = chunk_size if cell_stride is None else cell_stride
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        n = 0 if stripes is None else len(stripes)
+        arr = None if stripes is None else (c_int * max(1, n))(*[int(c) for c in stripes])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_repair(self._h, a, b, chunk_size, stride, n, arr, int(bool(apply)),
+                                                  ctypes.byref(h)),
+            "rs_plan_repair",
+        )
+        return RepairPlan(h, (self, lofi, parity))
+
     def locate_syndrome(self, chunk_id: int, syndrome) -> int:
         """The member whose single wrong byte gives this syndrome column (e
         bytes: stored parity ^ parity of stored data) in stripe chunk_id, or
@@ -258,6 +305,15 @@ def xor_plan_verify(ranks: int, lofi, xorc, chunk_size: int, cell_stride: Option
         "xor_plan_verify",
     )
     return VerifyPlan(h, (lofi, xorc))
+
+
+def xor_plan_repair(ranks: int, lofi, xorc, chunk_size: int, cell_stride: Optional[int] = None, stripes=None,
+                    apply: bool = True):
+    """There is none: an XOR stripe has one parity row, which says that a
+    column is wrong and not which cell. Always raises; the tool for an XOR
+    set is a rebuild of the member its checksum sidecar names."""
+    raise _lib.RedsetHipError("xor_plan_repair: one parity row locates nothing; rebuild the member that the "
+                              "checksum sidecar names (verify_set(checksums=True), rebuild_set)")
 
 
 def gf_combine(inputs, outputs, coeffs: np.ndarray, nbytes: int, accumulate: bool = False, stream=None) -> None:

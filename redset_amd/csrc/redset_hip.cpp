@@ -22,6 +22,7 @@
 #include "codec_kernels.h"
 #include "crc32.h"
 #include "gf256.h"
+#include "repair.h"
 #include "stripe_map.h"
 
 using redset_hip::CellRef;
@@ -66,6 +67,11 @@ struct redset_hip_plan {
   // tables (ranges, tile numbering, one remainder per tile, the CRCs)
   redset_hip::CrcLaunch crc{};
   void* d_crc = nullptr;
+  // repair plans (REDSET_HIP_PLAN_RS_REPAIR): the launch over the plan's
+  // device job blob, and both reports in one allocation
+  redset_hip::RepairLaunch repair{};
+  void* d_repair = nullptr;
+  unsigned long long* d_repair_report = nullptr;
 };
 
 namespace {
@@ -1120,6 +1126,99 @@ int redset_hip_plan_crc32_report(const redset_hip_plan* plan, void* stream, unsi
   return hip_check(hipStreamSynchronize(s), "crc32 report sync");
 }
 
+int redset_hip_rs_plan_repair(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                              size_t chunk_size, size_t stride, int nstripes, const int* stripes, int apply,
+                              redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  const int p = rs->ranks, e = rs->encoding, d = p - e;
+  if (e < 2)
+    return fail("plan_repair: encoding %d: one parity row locates nothing (rebuild the member a checksum names)", e);
+  if (e > kMaxOut) return fail("plan_repair: encoding %d: repair is built for 2..%d parity rows", e, kMaxOut);
+  if (!stripes) nstripes = p;
+  if (nstripes < 0 || nstripes > p) return fail("plan_repair: %d stripes of a set of %d", nstripes, p);
+  std::vector<char> seen(static_cast<size_t>(p), 0);
+  std::vector<redset_hip::RepairJobDesc> jobs(static_cast<size_t>(nstripes));
+  const SetLayout L{lofi, parity, stride};
+  for (int k = 0; k < nstripes; ++k) {
+    const int c = stripes ? stripes[k] : k;
+    if (c < 0 || c >= p) return fail("plan_repair: stripe %d out of range", c);
+    if (seen[c]) return fail("plan_repair: stripe %d listed twice", c);
+    seen[c] = 1;
+    StripeMap m;
+    redset_hip::rs_verify_map(rs, c, m);
+    redset_hip::RepairJobDesc& J = jobs[static_cast<size_t>(k)];
+    for (const CellRef& r : m.in) J.data.push_back(L.at(r)), J.member.push_back(r.rank);
+    for (const CellRef& r : m.out) J.parity.push_back(L.at(r)), J.member.push_back(r.rank);
+    J.coef = m.coef;
+    J.row = k;
+    if (static_cast<int>(J.data.size()) != d || static_cast<int>(J.parity.size()) != e)
+      return fail("plan_repair: stripe %d has %zu data and %zu parity cells", c, J.data.size(), J.parity.size());
+  }
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = REDSET_HIP_PLAN_RS_REPAIR;
+  plan->info.ranks = p;
+  plan->info.encoding = e;
+  plan->info.chunk_size = chunk_size;
+  plan->info.jobs = nstripes;
+  plan->info.launches = nstripes > 0 && chunk_size > 0 ? 2 : 1;
+  plan->info.bytes_read = static_cast<unsigned long long>(nstripes) * p * chunk_size;
+  redset_hip::RepairLaunch& R = plan->repair;
+  R.njobs = nstripes;
+  R.d = d;
+  R.e = e;
+  R.p = p;
+  R.apply = apply ? 1 : 0;
+  R.nbytes = chunk_size;
+  R.base = 0;
+  R.ncells = nstripes * p;
+  R.nstripes = nstripes;
+  const size_t words = 2 * static_cast<size_t>(R.ncells) + 2 * static_cast<size_t>(R.nstripes);
+  void* rp = nullptr;
+  int rc = hip_check(hipMalloc(&rp, std::max<size_t>(1, words) * sizeof(unsigned long long)), "hipMalloc(repair report)");
+  plan->d_repair_report = static_cast<unsigned long long*>(rp);
+  R.cell_report = plan->d_repair_report;
+  R.stripe_report = plan->d_repair_report + 2 * static_cast<size_t>(R.ncells);
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::repair_upload(jobs, d, e, &plan->d_repair, &R.jobs)),
+                           "repair plan upload");
+  // a report read before the first execute says "nothing found"
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::launch_repair_reset(R, nullptr)), "repair report reset");
+  rc = rc ? rc : hip_check(hipStreamSynchronize(nullptr), "repair report reset");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  R.blocks_per_job = redset_hip::repair_blocks_per_job(nstripes, chunk_size);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_repair_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells, int ncells,
+                                  redset_hip_repair_stripe* stripes, int nstripes) {
+  if (!plan) return fail("repair_report: null plan");
+  if (plan->info.kind != REDSET_HIP_PLAN_RS_REPAIR)
+    return fail("repair_report: not a repair plan (kind %d)", plan->info.kind);
+  const redset_hip::RepairLaunch& R = plan->repair;
+  if (cells && ncells < R.ncells) return fail("repair_report: room for %d cells, the plan reports %d", ncells, R.ncells);
+  if (stripes && nstripes < R.nstripes)
+    return fail("repair_report: room for %d stripes, the plan reports %d", nstripes, R.nstripes);
+  const size_t nc = static_cast<size_t>(R.ncells), ns = static_cast<size_t>(R.nstripes);
+  std::vector<unsigned long long> raw(2 * nc + 2 * ns);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!raw.empty())
+    if (int rc = hip_check(hipMemcpyAsync(raw.data(), plan->d_repair_report, raw.size() * sizeof(unsigned long long),
+                                          hipMemcpyDeviceToHost, s),
+                           "repair report copy"))
+      return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "repair report sync")) return rc;
+  for (size_t i = 0; cells && i < nc; ++i) cells[i] = redset_hip_repair_cell{raw[i], raw[nc + i]};
+  for (size_t i = 0; stripes && i < ns; ++i) stripes[i] = redset_hip_repair_stripe{raw[2 * nc + i], raw[2 * nc + ns + i]};
+  return REDSET_SUCCESS;
+}
+
 int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   if (!plan) return fail("null plan");
   for (const auto& C : plan->gf_checks)
@@ -1135,6 +1234,11 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   }
   if (plan->info.kind == REDSET_HIP_PLAN_CRC32)
     return hip_check(static_cast<hipError_t>(redset_hip::launch_crc32(plan->crc, stream)), "crc32 launch");
+  if (plan->info.kind == REDSET_HIP_PLAN_RS_REPAIR) {
+    if (int e = redset_hip::launch_repair_reset(plan->repair, stream))
+      return hip_check(static_cast<hipError_t>(e), "repair report reset");
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_repair(plan->repair, stream)), "gf_repair launch");
+  }
   for (const GfLaunch& G : plan->gf_launches)
     if (int e = redset_hip::launch_gf(G, stream)) return hip_check(static_cast<hipError_t>(e), "gf_mac launch");
   for (const XorLaunch& X : plan->xor_launches)
@@ -1156,6 +1260,8 @@ void redset_hip_plan_destroy(redset_hip_plan* plan) {
   if (plan->d_report) (void) hipFree(plan->d_report);
   if (plan->d_scratch) (void) hipFree(plan->d_scratch);
   if (plan->d_crc) (void) hipFree(plan->d_crc);
+  if (plan->d_repair) (void) hipFree(plan->d_repair);
+  if (plan->d_repair_report) (void) hipFree(plan->d_repair_report);
   delete plan;
 }
 

@@ -283,6 +283,84 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
     return out
 
 
+def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: bool = True,
+               checksums: bool = False) -> Dict:
+    """Scrub one RS set on disk (2 <= e <= 4) and correct, in place, every
+    byte column with one wrong byte (redset_amd.stream.rs_repair_stream):
+    only the wrong bytes' cell slices are rewritten, and members each damaged
+    at different offsets are repaired even when they are more than a rebuild
+    has erasures for. Driven by the headers as verify_set is. Lost members
+    are rebuild_set's job and a ValueError here, as are XOR sets and e = 1
+    (one parity row locates nothing: rebuild the member the checksum sidecar
+    names) and e > 4.
+
+    A dry run comes first and says which members need corrections; with
+    ``apply`` only those members' data files are then opened for writing
+    (redundancy files are opened as every streaming call opens them and
+    written only where their payload is corrected; headers are never
+    touched). Files of members with nothing to correct keep their size,
+    modification time and inode. ``apply=False`` stops after the dry run.
+
+    Returns the scheme, the summary (``verify_mismatch_bytes``,
+    ``corrected_bytes``, ``unlocated_columns``, ``remaining_mismatch_bytes``,
+    ``damaged_stripes``, ``repair_units``, ``cells_written``) and ``damaged``:
+    per damaged stripe its number, ``members`` -- [{"member", "kind": "data" |
+    "parity", "corrected_bytes", "first_offset"}] -- and
+    ``unlocated_columns``. ``repaired`` is true iff nothing mismatches after
+    the call and no column was unlocated.
+    ``checksums``: afterwards recompute every member's CRC-32s (one
+    crc32_stream pass) and compare them with the stored sidecar (apply_set(
+    checksums=True); none readable: ValueError before anything is written).
+    ``checksum_damaged`` lists what differs; any entry makes ``repaired``
+    false -- the guard against e = 2's miscorrection of a column with two
+    wrong bytes into a third member. Sidecars are not rewritten: a correct
+    repair restores the recorded bytes."""
+    f, reds, files, lost = _read_set(redundancy_files)
+    p, k = f.ranks, f.encoding
+    if lost:
+        raise ValueError(f"members {lost} are lost: rebuild_set them, repair_set corrects bytes of members that are there")
+    if f.scheme != "RS" or k < 2:
+        raise ValueError(f"{f.scheme} set with {k} parity row(s): one row locates nothing; the tool here is a "
+                         "rebuild (rebuild_set) of the member that the checksum sidecar names "
+                         "(verify_set(checksums=True))")
+    if k > 4:
+        raise ValueError(f"RS set with {k} parity rows: repair is built for 2..4; rebuild_set the located member")
+    stored = _read_sidecar(reds, p, f.chunk) if checksums else None
+    hsize = [f.header_size[r] for r in range(p)]
+    codec = _codec("RS", p, k)
+
+    def run(writable, do_apply):
+        io = stream.FileIO(files, reds, hsize, f.chunk, writable=writable)
+        try:
+            return stream.rs_repair_stream(codec, f.chunk, io, slice_bytes=slice_bytes, apply=do_apply)
+        finally:
+            io.close()
+
+    res = run(None, False)
+    if apply and res["corrected"].any():
+        # members with a correction in one of their data cells
+        data_fix = [any(res["corrected"][c, m] and codec.encoding_id(m, c) < p for c in range(p)) for m in range(p)]
+        res = run(data_fix, True)
+    out = {"scheme": f.scheme, "ranks": p, "encoding": k, "chunk": f.chunk, "applied": bool(apply), "damaged": [],
+           "stats": res["stats"]}
+    for key in ("verify_mismatch_bytes", "corrected_bytes", "unlocated_columns", "remaining_mismatch_bytes",
+                "damaged_stripes", "repair_units", "cells_written"):
+        out[key] = int(res[key])
+    for c in range(p):
+        if not res["corrected"][c].any() and not res["unlocated"][c]:
+            continue
+        members = [{"member": m, "kind": "data" if codec.encoding_id(m, c) < p else "parity",
+                    "corrected_bytes": int(res["corrected"][c, m]), "first_offset": int(res["first"][c, m])}
+                   for m in range(p) if res["corrected"][c, m]]
+        out["damaged"].append({"stripe": c, "members": members, "unlocated_columns": int(res["unlocated"][c])})
+    out["repaired"] = out["remaining_mismatch_bytes"] == 0 and out["unlocated_columns"] == 0
+    if stored is not None:
+        now = _checksum_table(files, reds, hsize, f.chunk, k, slice_bytes)
+        out["checksum_damaged"] = _checksum_diff(stored, now, reds)
+        out["repaired"] = out["repaired"] and not out["checksum_damaged"]
+    return out
+
+
 def _gf_mul(a: int, b: int) -> int:
     """GF(2^8) / 0x11D product (the codec's field)."""
     r = 0
@@ -336,8 +414,9 @@ def verify_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums:
     parity rows) and ``damaged``: per damaged stripe its number, the first
     differing cell ``offset``, the located ``member`` (None for XOR sets or
     when no single member explains the column) and whether that member's
-    wrong cell is ``"data"`` or ``"parity"``. A located member is repaired by
-    removing its files and calling rebuild_set.
+    wrong cell is ``"data"`` or ``"parity"``. Damage is repaired in place by
+    repair_set (RS sets with 2 <= e <= 4: every byte column with one wrong
+    byte), or by removing a located member's files and calling rebuild_set.
     ``checksums``: also recompute every member's CRC-32s (one crc32_stream
     pass) and compare them with the set's checksum sidecar (apply_set(
     checksums=True); none readable: ValueError). ``checksum_damaged`` lists

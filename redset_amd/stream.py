@@ -121,6 +121,32 @@ def xor_verify_stream(ranks: int, chunk: int, io, first: int = 0, nstripes: int 
                    io_threads, ctypes.byref(io.io))
 
 
+def rs_repair_stream(codec, chunk: int, io, first: int = 0, nstripes: int = 0, slice_bytes: int = 0,
+                     io_threads: int = 0, apply: bool = True) -> dict:
+    """Scrub a host-resident RS set (2 <= e <= 4) and correct every byte
+    column with one wrong byte (include/redset_hip.h
+    redset_hip_rs_repair_stream): the verify stream first -- a clean set ends
+    there -- then the damaged stripes slice by slice through the repair
+    kernel, writing back (``apply``) only the corrected cells' slices, then
+    the check again. Returns the summary's fields, ``corrected`` / ``first``
+    [stripes of the call, p], ``unlocated`` / ``first_unlocated`` [stripes of
+    the call] (see codec.RepairPlan.report) and the statistics."""
+    from .codec import repair_arrays
+
+    n, p = (nstripes if nstripes > 0 else codec.ranks), codec.ranks
+    st, summ = _lib.StreamStats(), _lib.RepairSummary()
+    cells = (_lib.RepairCell * max(1, n * p))()
+    stripes = (_lib.RepairStripe * max(1, n))()
+    _lib.check(_lib.load().redset_hip_rs_repair_stream(
+        codec._h, chunk, first, nstripes, slice_bytes, io_threads, ctypes.byref(io.io), int(bool(apply)),
+        ctypes.byref(st), cells, n * p, stripes, n, ctypes.byref(summ)), "rs_repair_stream")
+    corrected, first_off, unloc, first_unloc = repair_arrays(cells, stripes, n, p)
+    out = summ.as_dict()
+    out.update({"corrected": corrected, "first": first_off, "unlocated": unloc, "first_unlocated": first_unloc,
+                "stats": st.as_dict()})
+    return out
+
+
 def crc32_stream(chunk: int, io, spans: Sequence[Tuple[int, int, int, int]], slice_bytes: int = 0,
                  io_threads: int = 0) -> dict:
     """zlib CRC-32 of every span ``(rank, kind, offset, length)`` of a
