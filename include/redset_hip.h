@@ -51,7 +51,8 @@ enum {
   REDSET_HIP_PLAN_RS_VERIFY = 5,
   REDSET_HIP_PLAN_XOR_VERIFY = 6,
   REDSET_HIP_PLAN_CRC32 = 7,
-  REDSET_HIP_PLAN_RS_REPAIR = 8
+  REDSET_HIP_PLAN_RS_REPAIR = 8,
+  REDSET_HIP_PLAN_RS_REBUILD_CHECKED = 9
 };
 
 typedef struct {
@@ -240,11 +241,81 @@ int redset_hip_plan_repair_report(const redset_hip_plan* plan, void* stream, red
 
 typedef struct { unsigned long long verify_mismatch_bytes, corrected_bytes, unlocated_columns,
                  remaining_mismatch_bytes; int damaged_stripes, repair_units, cells_written; } redset_hip_repair_summary;
+
+/* ---- checked rebuild (errors-and-erasures decode) ---------------------- */
+/*
+ * A rebuild that checks its survivors. With k lost members of an RS set,
+ * 0 < k < e <= 4, the e - k parity rows a rebuild does not need form a
+ * checkable code over the d + e - k surviving cells of every byte column
+ * (distance e - k + 1). Capability per e - k: >= 2, one wrong survivor byte
+ * per column is located and taken out of the rebuilt bytes; >= 3, two wrong
+ * survivor bytes in a column are detected (unlocated); == 2, two wrong bytes
+ * may be unlocated or MIScorrected (the member checksums arbitrate,
+ * setfiles.rebuild_set checksums=True); == 1, damage is detected, never
+ * located. k == 0 is the repair plan's case, k == e the plain rebuild's.
+ *
+ * The arithmetic, per stripe: H = [A | I], e x (d + e), A the stripe's parity
+ * coefficients as the verify and repair plans use them; column i < d is data
+ * input i (the data-holding members in ascending order), column d + j parity
+ * row j. M = W * H with W invertible and W * H_L = [0 ; I_k] on the lost
+ * members' columns L: rows 0 .. e-k-1 (check rows, G) vanish on L, rows
+ * e-k .. e-1 (rebuild rows, B) are the identity on L and, on the survivors,
+ * exactly redset_hip_rs_decode_matrix's coefficients. R = sum over survivors
+ * of G_m * c_m is the reduced syndrome (zero for consistent survivors),
+ * v = sum over survivors of B_m * c_m what redset_hip_rs_plan_rebuild stores.
+ */
+
+/* M for stripe chunk_id: mat_out e x (d + e) bytes row-major, check rows
+ * first; cols_lost_out (may be NULL): the column of rebuild_ranks[i].
+ * 1 <= missing <= e (missing == e: no check rows), ranks ascending. Host only. */
+int redset_hip_rs_check_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                               unsigned char* mat_out, int* cols_lost_out);
+/* Locate (host; the rule the kernel applies literally): reduced_syndrome is
+ * the e - k bytes R of one byte column. For each surviving column m in
+ * order: j0 = the first check row with G[j0][m] != 0, x = R[j0] / G[j0][m];
+ * m explains the column when x != 0 and G[j][m] * x == R[j] in every check
+ * row. Exactly one match: *member_out = the member holding that cell,
+ * *value_out (may be NULL) = x: that cell's byte is wrong by x and the
+ * rebuilt bytes by B_m * x. Otherwise (R zero, none or several match, always
+ * so with e - k == 1) -1 and 0. */
+int redset_hip_rs_locate_reduced(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                                 const unsigned char* reduced_syndrome, int* member_out, unsigned char* value_out);
+
+/* Checked rebuild plan over all p stripes: every lost cell gets its rebuilt
+ * bytes, with the error of a located survivor byte taken out before the
+ * store; unlocated columns store the bytes the plain rebuild would.
+ * fix_survivors != 0 also XORs the located survivor byte right (a one-byte
+ * read-modify-write); otherwise no survivor byte is written. Exactly
+ * chunk_size bytes of each lost cell are written, nothing in the padding up
+ * to cell_stride. Executes through redset_hip_plan_execute like any plan:
+ * two kernel launches (report reset, decode), no allocation, no host
+ * synchronisation (safe inside hipStreamBeginCapture), no block waits on
+ * another, so neither the ring nor the hang count can move. Plan info: kind
+ * 9, jobs = p, bytes_read = p * (d + e - k) * chunk_size, bytes_written =
+ * p * k * chunk_size. Refused at plan time: missing == 0, missing == e,
+ * missing > e, e > 4, duplicate, unsorted or out-of-range ranks. One plan
+ * must not execute on two streams at once. */
+int redset_hip_rs_plan_rebuild_checked(const redset_hip_rs* rs, int missing, const int* rebuild_ranks,
+                                       unsigned char* const* lofi, unsigned char* const* parity, size_t chunk_size,
+                                       size_t cell_stride, int fix_survivors, redset_hip_plan** out);
+/* The report of the plan's last execute, shaped as the repair plan's:
+ * cells[stripe * p + member] (ncells at least p * p): survivor bytes located
+ * as wrong (corrected with fix_survivors; their effect on the rebuilt bytes
+ * is removed either way) and the smallest such offset; stripes[stripe]
+ * (nstripes at least p): unlocated columns. Either may be NULL. Ordered on
+ * `stream` after the work already there; waits for it. */
+int redset_hip_plan_rebuild_checked_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells,
+                                           int ncells, redset_hip_repair_stripe* stripes, int nstripes);
+
+typedef struct { unsigned long long corrected_bytes, unlocated_columns;
+                 int stripes_with_findings, cells_written; } redset_hip_rebuild_checked_summary;
+
 /* ---- member checksums (zlib CRC-32 on the device) --------------------- */
 /*
  * The parity says whether a stripe is consistent, not which bytes are wrong
  * (an XOR row names no cell; two wrong members may look like a third), and a
- * rebuild trusts every survivor. A content checksum per member answers both.
+ * plain rebuild trusts every survivor (the checked rebuild above does not,
+ * within its distance). A content checksum per member answers both.
  * It is the CRC-32 of zlib (reflected polynomial 0xEDB88320, initial value
  * and final XOR 0xFFFFFFFF, 0 for no bytes): what the reference computes in
  * redset_crc32 (src/redset_io.c:477-510) and never stored (the crc_on_copy
@@ -402,6 +473,25 @@ int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk_size, int 
                                 size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
                                 redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
                                 redset_hip_repair_stripe* stripes, int nstripes_out, redset_hip_repair_summary* summary);
+
+/* Checked rebuild of a host-resident set (memory or files, see "checked
+ * rebuild" above). For every stripe of the call and every slice,
+ * synchronously: io->read the survivors' slices, run the decode kernel on
+ * them (report offsets are cell offsets), io->write the k rebuilt slices
+ * and, with fix_survivors, only those survivor cells corrected in that
+ * slice, only that slice's range. cells[(stripe - first_stripe) * p +
+ * member] and stripes[stripe - first_stripe] are summed over the slices
+ * (each may be NULL); summary: corrected survivor bytes, unlocated columns,
+ * stripes with any finding, and cells written (rebuilt and corrected
+ * slices). Refuses what the plan refuses. Returns REDSET_SUCCESS when the
+ * rebuild RAN (findings are in the outputs). Device and pinned memory are
+ * allocated per call and freed on every way out. */
+int redset_hip_rs_rebuild_checked_stream(const redset_hip_rs* rs, int missing, const int* rebuild_ranks,
+                                         size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
+                                         int io_threads, const redset_hip_io* io, int fix_survivors,
+                                         redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
+                                         redset_hip_repair_stripe* stripes, int nstripes_out,
+                                         redset_hip_rebuild_checked_summary* summary);
 
 /* CRC-32 of byte spans of a host-resident set, in the members' own
  * coordinates: the same read -> H2D -> kernel pipeline with the CRC kernels,

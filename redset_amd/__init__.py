@@ -12,6 +12,7 @@ from ._lib import LIB_PATH, RedsetHipError, RedsetHipUnavailable, load  # noqa: 
 from .codec import (  # noqa: F401
     Plan,
     RSCodec,
+    RebuildCheckedPlan,
     RepairPlan,
     SetLayout,
     VerifyPlan,
@@ -26,7 +27,7 @@ from .codec import (  # noqa: F401
     xor_plan_verify,
 )
 from .checksum import Crc32Plan, crc32_combine  # noqa: F401
-from .setfiles import repair_set, verify_set  # noqa: F401
-from .stream import rs_repair_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
+from .setfiles import rebuild_set, repair_set, verify_set  # noqa: F401
+from .stream import rs_rebuild_checked_stream, rs_repair_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
 
 __version__ = "0.1.0"

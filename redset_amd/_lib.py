@@ -27,6 +27,7 @@ PLAN_RS_VERIFY = 5
 PLAN_XOR_VERIFY = 6
 PLAN_CRC32 = 7
 PLAN_RS_REPAIR = 8
+PLAN_RS_REBUILD_CHECKED = 9
 
 # every symbol include/redset_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -94,6 +95,11 @@ EXPORTED_SYMBOLS = (
     "redset_hip_rs_plan_repair",
     "redset_hip_plan_repair_report",
     "redset_hip_rs_repair_stream",
+    "redset_hip_rs_check_matrix",
+    "redset_hip_rs_locate_reduced",
+    "redset_hip_rs_plan_rebuild_checked",
+    "redset_hip_plan_rebuild_checked_report",
+    "redset_hip_rs_rebuild_checked_stream",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -162,6 +168,20 @@ class RepairSummary(ctypes.Structure):
         ("remaining_mismatch_bytes", c_ulonglong),
         ("damaged_stripes", c_int),
         ("repair_units", c_int),
+        ("cells_written", c_int),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RebuildCheckedSummary(ctypes.Structure):
+    """redset_hip_rebuild_checked_summary: totals of one redset_hip_rs_rebuild_checked_stream call."""
+
+    _fields_ = [
+        ("corrected_bytes", c_ulonglong),
+        ("unlocated_columns", c_ulonglong),
+        ("stripes_with_findings", c_int),
         ("cells_written", c_int),
     ]
 
@@ -388,6 +408,16 @@ _SIGNATURES = {
     "redset_hip_rs_repair_stream": (
         c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, c_int, _STP, POINTER(RepairCell), c_int,
                 POINTER(RepairStripe), c_int, POINTER(RepairSummary)]),
+    "redset_hip_rs_check_matrix": (c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_ubyte), POINTER(c_int)]),
+    "redset_hip_rs_locate_reduced": (
+        c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_ubyte), POINTER(c_int), POINTER(c_ubyte)]),
+    "redset_hip_rs_plan_rebuild_checked": (
+        c_int, [c_void_p, c_int, POINTER(c_int), _PP, _PP, c_size_t, c_size_t, c_int, POINTER(c_void_p)]),
+    "redset_hip_plan_rebuild_checked_report": (
+        c_int, [c_void_p, c_void_p, POINTER(RepairCell), c_int, POINTER(RepairStripe), c_int]),
+    "redset_hip_rs_rebuild_checked_stream": (
+        c_int, [c_void_p, c_int, POINTER(c_int), c_size_t, c_int, c_int, c_size_t, c_int, _IOP, c_int, _STP,
+                POINTER(RepairCell), c_int, POINTER(RepairStripe), c_int, POINTER(RebuildCheckedSummary)]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

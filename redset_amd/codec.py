@@ -160,6 +160,26 @@ class RepairPlan(Plan):
         return repair_arrays(cells, stripes, n, p)
 
 
+class RebuildCheckedPlan(Plan):
+    """A checked rebuild plan: execute() rebuilds the lost members' cells
+    and, per byte column, locates one wrong survivor byte from the parity
+    rows the rebuild does not need and takes its error out of the rebuilt
+    bytes (include/redset_hip.h, "checked rebuild")."""
+
+    def report(self, stream=None):
+        """``(corrected, first, unlocated, first_unlocated)`` of the last
+        execute, shaped as RepairPlan.report with n = p: survivor bytes
+        located as wrong per (stripe, member) and the smallest such cell
+        offset, and per stripe the columns no single survivor explains.
+        Waits for the work on ``stream``."""
+        p = int(self.info.ranks)
+        cells = (_lib.RepairCell * (p * p))()
+        stripes = (_lib.RepairStripe * p)()
+        _lib.check(_lib.load().redset_hip_plan_rebuild_checked_report(self._h, _stream_handle(stream), cells, p * p,
+                                                                      stripes, p), "plan_rebuild_checked_report")
+        return repair_arrays(cells, stripes, p, p)
+
+
 class RSCodec:
     """GF(2^8) tables + encoding matrix for a set of ``ranks`` members with
     ``encoding`` parity cells per stripe (redset_construct_rs,
@@ -249,6 +269,52 @@ class RSCodec:
             "rs_plan_repair",
         )
         return RepairPlan(h, (self, lofi, parity))
+
+    def plan_rebuild_checked(self, rebuild_ranks: Sequence[int], lofi, parity, chunk_size: int,
+                             cell_stride: Optional[int] = None, fix_survivors: bool = False) -> "RebuildCheckedPlan":
+        """Rebuild the lost members and check the survivors against the spare
+        parity rows: 0 < len(rebuild_ranks) < e <= 4. ``fix_survivors`` also
+        corrects the located survivor bytes in place."""
+        stride = chunk_size if cell_stride is None else cell_stride
+        ranks = sorted(rebuild_ranks)
+        r = (c_int * max(1, len(ranks)))(*ranks)
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_rebuild_checked(self._h, len(ranks), r, a, b, chunk_size, stride,
+                                                           int(bool(fix_survivors)), ctypes.byref(h)),
+            "rs_plan_rebuild_checked",
+        )
+        return RebuildCheckedPlan(h, (self, lofi, parity))
+
+    def check_matrix(self, rebuild_ranks: Sequence[int], chunk_id: int):
+        """``(M, lost_cols)`` of stripe chunk_id with these members lost: M is
+        [e, d + e] uint8 -- e - k check rows (zero on the lost columns), then
+        k rebuild rows (identity on them) -- over the stripe's cells (column
+        i < d: data input i, column d + j: parity row j); lost_cols[i] is the
+        column of sorted(rebuild_ranks)[i] (include/redset_hip.h
+        redset_hip_rs_check_matrix)."""
+        ranks = sorted(rebuild_ranks)
+        k, e, n = len(ranks), self.encoding, self.ranks
+        r = (c_int * max(1, k))(*ranks)
+        buf = (c_ubyte * (e * n))()
+        cols = (c_int * max(1, k))()
+        _lib.check(_lib.load().redset_hip_rs_check_matrix(self._h, k, r, chunk_id, buf, cols), "rs_check_matrix")
+        return np.frombuffer(bytes(buf), dtype=np.uint8).reshape(e, n).copy(), [int(c) for c in cols[:k]]
+
+    def locate_reduced(self, rebuild_ranks: Sequence[int], chunk_id: int, reduced_syndrome):
+        """``(member, value)``: the one surviving member whose single wrong
+        byte gives this reduced syndrome (e - k bytes: the check rows of
+        check_matrix applied to the survivors' bytes of one column) and that
+        byte's error, or (-1, 0) (include/redset_hip.h
+        redset_hip_rs_locate_reduced)."""
+        ranks = sorted(rebuild_ranks)
+        r = (c_int * max(1, len(ranks)))(*ranks)
+        syn = (c_ubyte * max(1, len(reduced_syndrome)))(*[int(x) for x in reduced_syndrome])
+        m, x = c_int(-1), c_ubyte(0)
+        _lib.check(_lib.load().redset_hip_rs_locate_reduced(self._h, len(ranks), r, chunk_id, syn, ctypes.byref(m),
+                                                            ctypes.byref(x)), "rs_locate_reduced")
+        return int(m.value), int(x.value)
 
     def locate_syndrome(self, chunk_id: int, syndrome) -> int:
         """The member whose single wrong byte gives this syndrome column (e

@@ -22,6 +22,7 @@
 #include "codec_kernels.h"
 #include "crc32.h"
 #include "gf256.h"
+#include "rebuild_checked.h"
 #include "repair.h"
 #include "stripe_map.h"
 
@@ -72,6 +73,10 @@ struct redset_hip_plan {
   redset_hip::RepairLaunch repair{};
   void* d_repair = nullptr;
   unsigned long long* d_repair_report = nullptr;
+  // checked rebuild plans (REDSET_HIP_PLAN_RS_REBUILD_CHECKED): the same
+  redset_hip::CheckedLaunch checked{};
+  void* d_checked = nullptr;
+  unsigned long long* d_checked_report = nullptr;
 };
 
 namespace {
@@ -1219,6 +1224,128 @@ int redset_hip_plan_repair_report(const redset_hip_plan* plan, void* stream, red
   return REDSET_SUCCESS;
 }
 
+int redset_hip_rs_check_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                               unsigned char* mat_out, int* cols_lost_out) {
+  if (!rs || !mat_out) return fail("check_matrix: null argument");
+  redset_hip::CheckMatrix X;
+  if (int rc = redset_hip::rs_check_matrix(rs, missing, rebuild_ranks, chunk_id, X)) return rc;
+  std::memcpy(mat_out, X.M.data(), X.M.size());
+  for (int i = 0; cols_lost_out && i < missing; ++i) cols_lost_out[i] = X.lost_cols[static_cast<size_t>(i)];
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_locate_reduced(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                                 const unsigned char* reduced_syndrome, int* member_out, unsigned char* value_out) {
+  if (!rs || !reduced_syndrome || !member_out) return fail("locate_reduced: null argument");
+  *member_out = -1;
+  if (value_out) *value_out = 0;
+  redset_hip::CheckMatrix X;
+  if (int rc = redset_hip::rs_check_matrix(rs, missing, rebuild_ranks, chunk_id, X)) return rc;
+  int col = -1;
+  uint8_t x = 0;
+  redset_hip::locate_reduced(X, reduced_syndrome, &col, &x);
+  if (col >= 0) {
+    *member_out = X.cells[static_cast<size_t>(col)].rank;
+    if (value_out) *value_out = x;
+  }
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_plan_rebuild_checked(const redset_hip_rs* rs, int missing, const int* rebuild_ranks,
+                                       unsigned char* const* lofi, unsigned char* const* parity, size_t chunk_size,
+                                       size_t stride, int fix_survivors, redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  const int p = rs->ranks, e = rs->encoding, k = missing, ns = p - k;
+  if (e > kMaxOut)
+    return fail("plan_rebuild_checked: encoding %d: the checked rebuild is built for 2..%d parity rows", e, kMaxOut);
+  if (k == 0) return fail("plan_rebuild_checked: no member is lost (use the repair plan, redset_hip_rs_plan_repair)");
+  if (k < 0 || k > e) return fail("plan_rebuild_checked: cannot rebuild %d members with %d parity chunks", k, e);
+  if (k == e)
+    return fail("plan_rebuild_checked: %d lost members of %d parity rows: nothing left to check (use the rebuild "
+                "plan, redset_hip_rs_plan_rebuild)", k, e);
+  std::vector<redset_hip::CheckedJobDesc> jobs(static_cast<size_t>(p));
+  const SetLayout L{lofi, parity, stride};
+  for (int c = 0; c < p; ++c) {
+    redset_hip::CheckMatrix X;
+    if (int rc = redset_hip::rs_check_matrix(rs, k, rebuild_ranks, c, X)) return rc;
+    redset_hip::CheckedJobDesc& J = jobs[static_cast<size_t>(c)];
+    std::vector<int> cols;
+    for (int i = 0; i < p; ++i)
+      if (std::find(X.lost_cols.begin(), X.lost_cols.end(), i) == X.lost_cols.end()) cols.push_back(i);
+    for (int i : cols) J.in.push_back(L.at(X.cells[static_cast<size_t>(i)])), J.member.push_back(X.cells[static_cast<size_t>(i)].rank);
+    for (int i : X.lost_cols) J.out.push_back(L.at(X.cells[static_cast<size_t>(i)]));
+    for (int j = 0; j < e; ++j)
+      for (int i : cols) J.coef.push_back(X.M[static_cast<size_t>(j) * p + i]);
+    J.row = c;
+  }
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = REDSET_HIP_PLAN_RS_REBUILD_CHECKED;
+  plan->info.ranks = p;
+  plan->info.encoding = e;
+  plan->info.missing = k;
+  plan->info.chunk_size = chunk_size;
+  plan->info.jobs = p;
+  plan->info.launches = chunk_size > 0 ? 2 : 1;
+  plan->info.bytes_read = static_cast<unsigned long long>(p) * ns * chunk_size;
+  plan->info.bytes_written = static_cast<unsigned long long>(p) * k * chunk_size;
+  redset_hip::CheckedLaunch& R = plan->checked;
+  R.njobs = p;
+  R.ns = ns;
+  R.e = e;
+  R.k = k;
+  R.p = p;
+  R.fix_survivors = fix_survivors ? 1 : 0;
+  R.nbytes = chunk_size;
+  R.base = 0;
+  R.ncells = p * p;
+  R.nstripes = p;
+  const size_t words = 2 * static_cast<size_t>(R.ncells) + 2 * static_cast<size_t>(R.nstripes);
+  void* rp = nullptr;
+  int rc = hip_check(hipMalloc(&rp, words * sizeof(unsigned long long)), "hipMalloc(checked rebuild report)");
+  plan->d_checked_report = static_cast<unsigned long long*>(rp);
+  R.cell_report = plan->d_checked_report;
+  R.stripe_report = plan->d_checked_report + 2 * static_cast<size_t>(R.ncells);
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::checked_upload(jobs, ns, e, k, &plan->d_checked, &R.jobs)),
+                           "checked rebuild plan upload");
+  // a report read before the first execute says "nothing found"
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::launch_checked_reset(R, nullptr)), "checked rebuild report reset");
+  rc = rc ? rc : hip_check(hipStreamSynchronize(nullptr), "checked rebuild report reset");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  R.blocks_per_job = redset_hip::checked_blocks_per_job(p, chunk_size);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_rebuild_checked_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells,
+                                           int ncells, redset_hip_repair_stripe* stripes, int nstripes) {
+  if (!plan) return fail("rebuild_checked_report: null plan");
+  if (plan->info.kind != REDSET_HIP_PLAN_RS_REBUILD_CHECKED)
+    return fail("rebuild_checked_report: not a checked rebuild plan (kind %d)", plan->info.kind);
+  const redset_hip::CheckedLaunch& R = plan->checked;
+  if (cells && ncells < R.ncells)
+    return fail("rebuild_checked_report: room for %d cells, the plan reports %d", ncells, R.ncells);
+  if (stripes && nstripes < R.nstripes)
+    return fail("rebuild_checked_report: room for %d stripes, the plan reports %d", nstripes, R.nstripes);
+  const size_t nc = static_cast<size_t>(R.ncells), ns = static_cast<size_t>(R.nstripes);
+  std::vector<unsigned long long> raw(2 * nc + 2 * ns);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = hip_check(hipMemcpyAsync(raw.data(), plan->d_checked_report, raw.size() * sizeof(unsigned long long),
+                                        hipMemcpyDeviceToHost, s),
+                         "checked rebuild report copy"))
+    return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "checked rebuild report sync")) return rc;
+  for (size_t i = 0; cells && i < nc; ++i) cells[i] = redset_hip_repair_cell{raw[i], raw[nc + i]};
+  for (size_t i = 0; stripes && i < ns; ++i) stripes[i] = redset_hip_repair_stripe{raw[2 * nc + i], raw[2 * nc + ns + i]};
+  return REDSET_SUCCESS;
+}
+
 int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   if (!plan) return fail("null plan");
   for (const auto& C : plan->gf_checks)
@@ -1238,6 +1365,12 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
     if (int e = redset_hip::launch_repair_reset(plan->repair, stream))
       return hip_check(static_cast<hipError_t>(e), "repair report reset");
     return hip_check(static_cast<hipError_t>(redset_hip::launch_repair(plan->repair, stream)), "gf_repair launch");
+  }
+  if (plan->info.kind == REDSET_HIP_PLAN_RS_REBUILD_CHECKED) {
+    if (int e = redset_hip::launch_checked_reset(plan->checked, stream))
+      return hip_check(static_cast<hipError_t>(e), "checked rebuild report reset");
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_checked(plan->checked, stream)),
+                     "gf_rebuild_checked launch");
   }
   for (const GfLaunch& G : plan->gf_launches)
     if (int e = redset_hip::launch_gf(G, stream)) return hip_check(static_cast<hipError_t>(e), "gf_mac launch");
@@ -1262,6 +1395,8 @@ void redset_hip_plan_destroy(redset_hip_plan* plan) {
   if (plan->d_crc) (void) hipFree(plan->d_crc);
   if (plan->d_repair) (void) hipFree(plan->d_repair);
   if (plan->d_repair_report) (void) hipFree(plan->d_repair_report);
+  if (plan->d_checked) (void) hipFree(plan->d_checked);
+  if (plan->d_checked_report) (void) hipFree(plan->d_checked_report);
   delete plan;
 }
 

@@ -1,6 +1,7 @@
 // stripe_map.cpp -- see stripe_map.h.
 #include "stripe_map.h"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -117,6 +118,96 @@ int rs_rebuild_map(const redset_hip_rs* rs, int missing, const int* rebuild_rank
     for (int s : cols) m.coef.push_back(D[static_cast<size_t>(i) * p + s]);
   }
   return 0;
+}
+
+int rs_check_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int c, CheckMatrix& X) {
+  const int p = rs->ranks, e = rs->encoding, d = p - e, n = p;
+  const Field& F = field();
+  if (c < 0 || c >= p) return fail("check_matrix: chunk id %d out of range", c);
+  if (missing < 1 || missing > e) return fail("check_matrix: %d lost members with %d parity rows", missing, e);
+  if (!rebuild_ranks) return fail("check_matrix: null rebuild_ranks");
+  std::vector<char> erased(static_cast<size_t>(p), 0);
+  for (int i = 0; i < missing; ++i) {
+    const int r = rebuild_ranks[i];
+    if (r < 0 || r >= p) return fail("check_matrix: rebuild rank %d out of range", r);
+    if (erased[r]) return fail("check_matrix: rebuild rank %d listed twice", r);
+    erased[r] = 1;
+  }
+  std::vector<uint8_t> D;
+  if (int rc = rs_decode_matrix(rs, missing, rebuild_ranks, c, D)) return rc;
+  StripeMap vm;
+  rs_verify_map(rs, c, vm);
+  X = CheckMatrix();
+  X.d = d;
+  X.e = e;
+  X.k = missing;
+  X.cells = vm.in;
+  X.cells.insert(X.cells.end(), vm.out.begin(), vm.out.end());
+  std::vector<int> col_of(static_cast<size_t>(p), -1);
+  for (int i = 0; i < n; ++i) col_of[X.cells[i].rank] = i;
+  for (int i = 0; i < missing; ++i) X.lost_cols.push_back(col_of[rebuild_ranks[i]]);
+  // H = [A | I], then eliminate the lost columns: the rows left without a
+  // pivot vanish on them
+  std::vector<uint8_t> H(static_cast<size_t>(e) * n, 0);
+  for (int j = 0; j < e; ++j) {
+    for (int i = 0; i < d; ++i) H[static_cast<size_t>(j) * n + i] = vm.coef[static_cast<size_t>(j) * d + i];
+    H[static_cast<size_t>(j) * n + d + j] = 1;
+  }
+  std::vector<char> used(static_cast<size_t>(e), 0);
+  for (int i = 0; i < missing; ++i) {
+    const int col = X.lost_cols[i];
+    int r = -1;
+    for (int j = 0; j < e && r < 0; ++j)
+      if (!used[j] && H[static_cast<size_t>(j) * n + col]) r = j;
+    if (r < 0) return fail("check_matrix: lost columns of stripe %d are dependent", c);
+    used[r] = 1;
+    const uint8_t s = F.inv(H[static_cast<size_t>(r) * n + col]);
+    for (int t = 0; t < n; ++t) H[static_cast<size_t>(r) * n + t] = F.mul(H[static_cast<size_t>(r) * n + t], s);
+    for (int j = 0; j < e; ++j) {
+      const uint8_t f = H[static_cast<size_t>(j) * n + col];
+      if (j == r || !f) continue;
+      for (int t = 0; t < n; ++t) H[static_cast<size_t>(j) * n + t] ^= F.mul(f, H[static_cast<size_t>(r) * n + t]);
+    }
+  }
+  X.M.assign(static_cast<size_t>(e) * n, 0);
+  int row = 0;
+  for (int j = 0; j < e; ++j)
+    if (!used[j]) std::copy(H.begin() + static_cast<size_t>(j) * n, H.begin() + static_cast<size_t>(j + 1) * n,
+                            X.M.begin() + static_cast<size_t>(row++) * n);
+  // the rebuild rows are the decode's own linear map, so an unchecked column
+  // gets the bytes the plain rebuild gives
+  for (int i = 0; i < missing; ++i, ++row) {
+    for (int s = 0; s < p; ++s)
+      if (!erased[s]) X.M[static_cast<size_t>(row) * n + col_of[s]] = D[static_cast<size_t>(i) * p + s];
+    X.M[static_cast<size_t>(row) * n + X.lost_cols[i]] = 1;
+  }
+  return 0;
+}
+
+void locate_reduced(const CheckMatrix& X, const uint8_t* R, int* col_out, uint8_t* value_out) {
+  const int n = X.d + X.e, nck = X.e - X.k;
+  const Field& F = field();
+  *col_out = -1;
+  *value_out = 0;
+  bool any = false;
+  for (int j = 0; j < nck; ++j) any = any || R[j] != 0;
+  if (!any || nck < 2) return;  // one check row: every survivor explains the column
+  int found = -1, matches = 0;
+  uint8_t val = 0;
+  for (int m = 0; m < n; ++m) {
+    bool lost = false;
+    for (int l : X.lost_cols) lost = lost || l == m;
+    if (lost) continue;
+    int j0 = -1;
+    for (int j = 0; j < nck && j0 < 0; ++j)
+      if (X.M[static_cast<size_t>(j) * n + m]) j0 = j;
+    if (j0 < 0) continue;
+    const uint8_t x = F.mul(R[j0], F.inv(X.M[static_cast<size_t>(j0) * n + m]));
+    bool ok = x != 0;
+    for (int j = 0; j < nck && ok; ++j) ok = F.mul(X.M[static_cast<size_t>(j) * n + m], x) == R[j];
+    if (ok) found = m, val = x, ++matches;
+  }
+  if (matches == 1) *col_out = found, *value_out = val;
 }
 
 namespace {

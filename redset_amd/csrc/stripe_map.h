@@ -55,6 +55,25 @@ int rs_rebuild_map(const redset_hip_rs* rs, int missing, const int* rebuild_rank
 // decode map of stripe c as (missing x p); column s = member s's cell
 int rs_decode_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int c, std::vector<uint8_t>& D);
 
+// Errors-and-erasures view of stripe c with `missing` lost members (ascending
+// ranks, 1 <= missing <= e): M = W * [A | I], e x (d + e), over the stripe's
+// cells in rs_verify_map order (column i < d: data input i, column d + j:
+// parity row j). Rows 0 .. e-missing-1 (check rows) vanish on the lost
+// members' columns; rows e-missing .. e-1 (rebuild rows) are the identity on
+// them and, on the survivors, exactly rs_decode_matrix's coefficients.
+struct CheckMatrix {
+  int d = 0, e = 0, k = 0;
+  std::vector<uint8_t> M;      // e x (d + e), row-major
+  std::vector<int> lost_cols;  // k: the column of rebuild_ranks[i]
+  std::vector<CellRef> cells;  // d + e: the cell of each column
+};
+int rs_check_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int c, CheckMatrix& out);
+// The locate rule over the check rows (include/redset_hip.h
+// redset_hip_rs_locate_reduced): *col_out = the one surviving column whose
+// single wrong byte gives the reduced syndrome R (e - k bytes), *value_out
+// that byte's error; -1 / 0 when R is zero or none or several columns match.
+void locate_reduced(const CheckMatrix& X, const uint8_t* R, int* col_out, uint8_t* value_out);
+
 // XOR stripe c: member c's parity = XOR of the other members' cells
 // (src/redset_xor.c:251-266); rebuild of `root` from all others.
 int xor_encode_map(int ranks, int c, StripeMap& m);

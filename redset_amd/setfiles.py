@@ -225,7 +225,8 @@ def _read_set(redundancy_files: Sequence[str]):
     return f, reds, files, lost
 
 
-def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums: bool = False) -> Dict:
+def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums: bool = False,
+                check_survivors: bool = False, fix_survivors: bool = False) -> Dict:
     """Rebuild the lost members of one set from the redundancy files that can
     still be read (``redundancy_files`` may name lost ones too). A member is
     lost when its redundancy file is unreadable or shorter than header + k
@@ -238,15 +239,41 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
     True)), every rebuilt data file and redundancy payload is checked against
     it after the rebuild -- a silently damaged survivor gives a wrong rebuild,
     reported in ``errors`` (``ok`` false) -- and the lost members' sidecars
-    are written again. No sidecar: a ValueError before anything is written."""
+    are written again. No sidecar: a ValueError before anything is written.
+
+    ``check_survivors``: rebuild through the checked rebuild
+    (redset_amd.stream.rs_rebuild_checked_stream) instead, for an RS set with
+    fewer lost members than parity rows, e <= 4: the parity rows the rebuild
+    does not need check the survivors of every byte column, and one wrong
+    survivor byte per column is located and kept out of the rebuilt files
+    (two spare rows or more; one spare row only detects). The result gains
+    ``survivor_corrections`` -- [{"member", "stripe", "bytes",
+    "first_offset"}] --, ``unlocated_columns``, ``unlocated_stripes`` and
+    ``trusted`` (false when any column is unlocated: its rebuilt bytes are
+    the plain rebuild's). XOR sets, as many lost members as parity rows and
+    e > 4 are a ValueError, never a silent plain rebuild. Survivors' data
+    files are opened read-only; with ``fix_survivors`` (which needs
+    check_survivors) a second pass opens for writing only the members the
+    first located corrections in, and writes the corrected bytes back."""
     f, reds, files, lost = _read_set(redundancy_files)
     p, k = f.ranks, f.encoding
     out = {"scheme": f.scheme, "ranks": p, "encoding": k, "chunk": f.chunk, "missing": lost,
            "redundancy": reds, "errors": []}
+    if fix_survivors and not check_survivors:
+        raise ValueError("fix_survivors needs check_survivors=True")
     if not lost:
         return out
     if len(lost) > k:
         raise ValueError(f"{len(lost)} members lost but {f.scheme} tolerates {k}")
+    if check_survivors:
+        if f.scheme != "RS":
+            raise ValueError(f"check_survivors: an {f.scheme} set has one parity row and the rebuild needs it; "
+                             "nothing is left to check the survivors with")
+        if k > 4:
+            raise ValueError(f"check_survivors: RS set with {k} parity rows: the checked rebuild is built for 2..4")
+        if len(lost) == k:
+            raise ValueError(f"check_survivors: {len(lost)} members lost of {k} parity rows: the rebuild needs every "
+                             "row, nothing is left to check the survivors with")
     stored = _read_sidecar(reds, p, f.chunk) if checksums else None
     hsize = [f.header_size.get(r, 0) for r in range(p)]
     for r in lost:
@@ -260,14 +287,39 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
             hsize[r] = H.write_header(fd, H.header_tree(f.scheme, r, f.members, f.world_ranks, f.chunk, k))
         finally:
             os.close(fd)
-    io = stream.FileIO(files, reds, hsize, f.chunk, writable=[r in lost for r in range(p)])
-    try:
-        if f.scheme == "RS":
-            out["stats"] = stream.rs_rebuild_stream(_codec("RS", p, k), lost, f.chunk, io, slice_bytes=slice_bytes)
-        else:
-            out["stats"] = stream.xor_rebuild_stream(p, lost[0], f.chunk, io, slice_bytes=slice_bytes)
-    finally:
-        io.close()
+    if check_survivors:
+        codec = _codec("RS", p, k)
+
+        def run(writable, fix):
+            cio = stream.FileIO(files, reds, hsize, f.chunk, writable=writable)
+            try:
+                return stream.rs_rebuild_checked_stream(codec, lost, f.chunk, cio, slice_bytes=slice_bytes,
+                                                        fix_survivors=fix)
+            finally:
+                cio.close()
+
+        res = run([r in lost for r in range(p)], False)
+        if fix_survivors and res["corrected"].any():
+            # members with a correction in one of their data cells
+            data_fix = [r in lost or any(res["corrected"][c, r] and codec.encoding_id(r, c) < p for c in range(p))
+                        for r in range(p)]
+            res = run(data_fix, True)
+        out["stats"] = res["stats"]
+        out["survivor_corrections"] = [
+            {"member": m, "stripe": c, "bytes": int(res["corrected"][c, m]), "first_offset": int(res["first"][c, m])}
+            for c in range(p) for m in range(p) if res["corrected"][c, m]]
+        out["unlocated_columns"] = int(res["unlocated_columns"])
+        out["unlocated_stripes"] = [c for c in range(p) if res["unlocated"][c]]
+        out["trusted"] = out["unlocated_columns"] == 0
+    else:
+        io = stream.FileIO(files, reds, hsize, f.chunk, writable=[r in lost for r in range(p)])
+        try:
+            if f.scheme == "RS":
+                out["stats"] = stream.rs_rebuild_stream(_codec("RS", p, k), lost, f.chunk, io, slice_bytes=slice_bytes)
+            else:
+                out["stats"] = stream.xor_rebuild_stream(p, lost[0], f.chunk, io, slice_bytes=slice_bytes)
+        finally:
+            io.close()
     for r in lost:
         for i, (path, _) in enumerate(files[r]):
             (_, meta), = f.members[r]["FILE"][str(i)].items()

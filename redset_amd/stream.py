@@ -147,6 +147,36 @@ def rs_repair_stream(codec, chunk: int, io, first: int = 0, nstripes: int = 0, s
     return out
 
 
+def rs_rebuild_checked_stream(codec, lost: Sequence[int], chunk: int, io, first: int = 0, nstripes: int = 0,
+                              slice_bytes: int = 0, io_threads: int = 0, fix_survivors: bool = False) -> dict:
+    """Rebuild the lost members of a host-resident RS set (0 < lost < e <= 4)
+    and check the survivors against the spare parity rows
+    (include/redset_hip.h redset_hip_rs_rebuild_checked_stream): one wrong
+    survivor byte per column is located and kept out of the rebuilt bytes
+    (e - k >= 2) and, with ``fix_survivors``, written back corrected. Returns
+    the summary's fields (``corrected_bytes``, ``unlocated_columns``,
+    ``stripes_with_findings``, ``cells_written``), ``corrected`` / ``first``
+    [stripes of the call, p], ``unlocated`` / ``first_unlocated`` [stripes of
+    the call] (see codec.RebuildCheckedPlan.report) and the statistics."""
+    from .codec import repair_arrays
+
+    r = sorted(lost)
+    arr = (c_int * max(1, len(r)))(*r)
+    n, p = (nstripes if nstripes > 0 else codec.ranks), codec.ranks
+    st, summ = _lib.StreamStats(), _lib.RebuildCheckedSummary()
+    cells = (_lib.RepairCell * max(1, n * p))()
+    stripes = (_lib.RepairStripe * max(1, n))()
+    _lib.check(_lib.load().redset_hip_rs_rebuild_checked_stream(
+        codec._h, len(r), arr, chunk, first, nstripes, slice_bytes, io_threads, ctypes.byref(io.io),
+        int(bool(fix_survivors)), ctypes.byref(st), cells, n * p, stripes, n, ctypes.byref(summ)),
+        "rs_rebuild_checked_stream")
+    corrected, first_off, unloc, first_unloc = repair_arrays(cells, stripes, n, p)
+    out = summ.as_dict()
+    out.update({"corrected": corrected, "first": first_off, "unlocated": unloc, "first_unlocated": first_unloc,
+                "stats": st.as_dict()})
+    return out
+
+
 def crc32_stream(chunk: int, io, spans: Sequence[Tuple[int, int, int, int]], slice_bytes: int = 0,
                  io_threads: int = 0) -> dict:
     """zlib CRC-32 of every span ``(rank, kind, offset, length)`` of a
