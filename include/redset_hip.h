@@ -52,7 +52,8 @@ enum {
   REDSET_HIP_PLAN_XOR_VERIFY = 6,
   REDSET_HIP_PLAN_CRC32 = 7,
   REDSET_HIP_PLAN_RS_REPAIR = 8,
-  REDSET_HIP_PLAN_RS_REBUILD_CHECKED = 9
+  REDSET_HIP_PLAN_RS_REBUILD_CHECKED = 9,
+  REDSET_HIP_PLAN_RS_REPAIR2 = 10
 };
 
 typedef struct {
@@ -208,6 +209,9 @@ int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int
  * e == 2 (distance 3), may be reported unlocated or MIScorrected into a third
  * member -- the member checksums below arbitrate (setfiles.repair_set
  * checksums=True). Columns no single member explains are left as found.
+ * e == 4 (distance 5) has a second, opt-in level, "repair2" below: a column
+ * with two wrong bytes is corrected as well, and a column with three may be
+ * reported unlocated or MIScorrected into another pair, as two are at e == 2.
  */
 typedef struct {
   unsigned long long corrected_bytes;  /* bytes of this member's cell of this stripe that were (apply) or would be (dry run) corrected */
@@ -241,6 +245,50 @@ int redset_hip_plan_repair_report(const redset_hip_plan* plan, void* stream, red
 
 typedef struct { unsigned long long verify_mismatch_bytes, corrected_bytes, unlocated_columns,
                  remaining_mismatch_bytes; int damaged_stripes, repair_units, cells_written; } redset_hip_repair_summary;
+
+/* ---- repair2 (two wrong bytes per column, e == 4 only) ----------------- */
+/*
+ * The encoding matrix is a Vandermonde matrix (row^col) brought to systematic
+ * form by column operations, so a stripe's byte column is a polynomial of
+ * degree < p evaluated at alpha = m for member m's data cell and alpha = p + j
+ * for parity row j; the members that hold parity in the stripe have their
+ * data point fixed at zero. With u_i = 1 / prod_{j != i} (alpha_i ^ alpha_j)
+ * over all p + e points, the rows u_i * alpha_i^t (t = 0 .. e-1, 0^0 = 1)
+ * span the row space of H = [A | I]: one e x e transform W^-1 turns the
+ * stored syndrome S into power sums S' = W^-1 S, and a column with two wrong
+ * bytes is solved in closed form (Peterson-Gorenstein-Zierler), not searched.
+ *
+ * power_basis (host): for stripe chunk_id, over the d + e cells in the order
+ * data inputs (ascending member) then parity rows, alpha[i] and u[i], and
+ * winv (e x e, row-major) with winv * H[:, i] = u[i] * (1, alpha[i],
+ * alpha[i]^2, alpha[i]^3). That identity is checked for every one of the
+ * d + e columns before the call returns and fails the call otherwise. e != 4
+ * is an error.
+ */
+int redset_hip_rs_power_basis(const redset_hip_rs* rs, int chunk_id, unsigned char* alpha, unsigned char* u,
+                              unsigned char* winv);
+/* The verdict on one byte column (host). A column redset_hip_rs_locate_syndrome
+ * locates keeps that answer (*count_out = 1). Otherwise S' = winv * S,
+ * D = S'0 S'2 ^ S'1^2 (0: unlocated), sigma2 = (S'2^2 ^ S'1 S'3) / D,
+ * sigma1 = (S'0 S'3 ^ S'1 S'2) / D, and the two distinct roots of
+ * z^2 ^ sigma1 z ^ sigma2 must both be points of cells of this stripe (0 is
+ * member 0's data cell); y1 = (S'0 X2 ^ S'1) / (X1 ^ X2), y2 = S'0 ^ y1, the
+ * error values are y / u, both nonzero. The pair is answered only if its own
+ * syndrome equals S: *count_out = 2, members_out ascending, values_out beside
+ * them. *count_out = 0: clean or unlocated. e != 4 is an error. */
+int redset_hip_rs_locate_syndrome2(const redset_hip_rs* rs, int chunk_id, const unsigned char* syndrome,
+                                   int* members_out, unsigned char* values_out, int* count_out);
+/* The repair plan with that verdict per column (gf_repair2_kernel): contract,
+ * report and plan info as redset_hip_rs_plan_repair (kind 10), both bytes of
+ * a pair corrected and counted, every correction applied only if its own
+ * syndrome equals the column's. e != 4 is REDSET_FAILURE. */
+int redset_hip_rs_plan_repair2(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                               size_t chunk_size, size_t cell_stride, int nstripes, const int* stripes /* NULL: all p */,
+                               int apply, redset_hip_plan** out);
+/* As redset_hip_plan_repair_report, plus pair_columns[k] (nstripes entries,
+ * may be NULL): the columns of planned stripe k corrected as a pair. */
+int redset_hip_plan_repair2_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells, int ncells,
+                                   redset_hip_repair_stripe* stripes, int nstripes, unsigned long long* pair_columns);
 
 /* ---- checked rebuild (errors-and-erasures decode) ---------------------- */
 /*
@@ -473,6 +521,13 @@ int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk_size, int 
                                 size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
                                 redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
                                 redset_hip_repair_stripe* stripes, int nstripes_out, redset_hip_repair_summary* summary);
+/* The same flow with the repair2 kernel (e == 4 only, see "repair2" above);
+ * *pair_columns_out (may be NULL) = the columns corrected as a pair. */
+int redset_hip_rs_repair2_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                 size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
+                                 redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
+                                 redset_hip_repair_stripe* stripes, int nstripes_out, redset_hip_repair_summary* summary,
+                                 unsigned long long* pair_columns_out);
 
 /* Checked rebuild of a host-resident set (memory or files, see "checked
  * rebuild" above). For every stripe of the call and every slice,

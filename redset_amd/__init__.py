@@ -13,6 +13,7 @@ from .codec import (  # noqa: F401
     Plan,
     RSCodec,
     RebuildCheckedPlan,
+    Repair2Plan,
     RepairPlan,
     SetLayout,
     VerifyPlan,

@@ -129,6 +129,15 @@ class VerifyPlan(Plan):
         return int(m.value), (None if off.value == NO_OFFSET else int(off.value))
 
 
+def check_max_errors(max_errors: int, encoding: int) -> None:
+    """The correction levels of repair: 1, or 2 on sets with four parity rows."""
+    if max_errors not in (1, 2):
+        raise ValueError(f"max_errors={max_errors}: repair corrects 1 or 2 wrong bytes per column")
+    if max_errors == 2 and encoding != 4:
+        raise ValueError(f"max_errors=2 on a set with {encoding} parity rows: two wrong bytes per column need "
+                         "distance 5, that is e = 4")
+
+
 def repair_arrays(cells, stripes, n: int, p: int):
     """(corrected[n, p], first[n, p], unlocated[n], first_unlocated[n]) of
     redset_hip_repair_cell / redset_hip_repair_stripe arrays."""
@@ -158,6 +167,24 @@ class RepairPlan(Plan):
         _lib.check(_lib.load().redset_hip_plan_repair_report(self._h, _stream_handle(stream), cells, n * p,
                                                              stripes, n), "plan_repair_report")
         return repair_arrays(cells, stripes, n, p)
+
+
+class Repair2Plan(Plan):
+    """A repair plan made with ``max_errors=2`` (RS sets with e = 4): columns
+    with two wrong bytes are corrected as well (include/redset_hip.h,
+    "repair2")."""
+
+    def report(self, stream=None):
+        """RepairPlan.report's four arrays -- both members of a pair are
+        counted -- and ``pair_columns`` [n]: the columns of each planned
+        stripe corrected as a pair. Waits for the work on ``stream``."""
+        n, p = int(self.info.jobs), int(self.info.ranks)
+        cells = (_lib.RepairCell * max(1, n * p))()
+        stripes = (_lib.RepairStripe * max(1, n))()
+        pairs = (ctypes.c_ulonglong * max(1, n))()
+        _lib.check(_lib.load().redset_hip_plan_repair2_report(self._h, _stream_handle(stream), cells, n * p,
+                                                              stripes, n, pairs), "plan_repair2_report")
+        return repair_arrays(cells, stripes, n, p) + (np.array(pairs[:n], dtype=np.uint64),)
 
 
 class RebuildCheckedPlan(Plan):
@@ -255,14 +282,24 @@ class RSCodec:
         return VerifyPlan(h, (self, lofi, parity))
 
     def plan_repair(self, lofi, parity, chunk_size: int, cell_stride: Optional[int] = None,
-                    stripes: Optional[Sequence[int]] = None, apply: bool = True) -> "RepairPlan":
+                    stripes: Optional[Sequence[int]] = None, apply: bool = True, max_errors: int = 1):
         """Correct, in the listed stripes (default: all), every byte column
-        with one wrong byte; ``apply=False`` only reports. 2 <= e <= 4."""
+        with one wrong byte; ``apply=False`` only reports. 2 <= e <= 4.
+        ``max_errors=2`` (e = 4 only, else ValueError) also corrects columns
+        with two wrong bytes and returns a Repair2Plan."""
+        check_max_errors(max_errors, self.encoding)
         stride = chunk_size if cell_stride is None else cell_stride
         a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
         n = 0 if stripes is None else len(stripes)
         arr = None if stripes is None else (c_int * max(1, n))(*[int(c) for c in stripes])
         h = c_void_p()
+        if max_errors == 2:
+            _lib.check(
+                _lib.load().redset_hip_rs_plan_repair2(self._h, a, b, chunk_size, stride, n, arr, int(bool(apply)),
+                                                       ctypes.byref(h)),
+                "rs_plan_repair2",
+            )
+            return Repair2Plan(h, (self, lofi, parity))
         _lib.check(
             _lib.load().redset_hip_rs_plan_repair(self._h, a, b, chunk_size, stride, n, arr, int(bool(apply)),
                                                   ctypes.byref(h)),
@@ -325,6 +362,28 @@ class RSCodec:
         _lib.check(_lib.load().redset_hip_rs_locate_syndrome(self._h, chunk_id, syn, ctypes.byref(m)),
                    "rs_locate_syndrome")
         return int(m.value)
+
+    def power_basis(self, chunk_id: int):
+        """``(alpha, u, winv)`` of stripe chunk_id (e = 4): the evaluation
+        point and dual multiplier of its d + e cells (data inputs, then parity
+        rows) and the [e, e] transform with winv @ H[:, i] = u[i] * alpha[i]^t
+        (include/redset_hip.h redset_hip_rs_power_basis)."""
+        n, e = self.ranks, self.encoding
+        alpha, u, winv = (c_ubyte * n)(), (c_ubyte * n)(), (c_ubyte * (e * e))()
+        _lib.check(_lib.load().redset_hip_rs_power_basis(self._h, chunk_id, alpha, u, winv), "rs_power_basis")
+        as_np = lambda b: np.frombuffer(bytes(b), dtype=np.uint8).copy()  # noqa: E731
+        return as_np(alpha), as_np(u), as_np(winv).reshape(e, e)
+
+    def locate_syndrome2(self, chunk_id: int, syndrome):
+        """``[(member, value), ...]``: the one or two members, ascending,
+        whose wrong bytes give this syndrome column in stripe chunk_id, with
+        the error values; empty when clean or unlocated (e = 4;
+        include/redset_hip.h redset_hip_rs_locate_syndrome2)."""
+        syn = (c_ubyte * max(4, self.encoding))(*[int(x) for x in syndrome])
+        mem, val, n = (c_int * 2)(), (c_ubyte * 2)(), c_int(0)
+        _lib.check(_lib.load().redset_hip_rs_locate_syndrome2(self._h, chunk_id, syn, mem, val, ctypes.byref(n)),
+                   "rs_locate_syndrome2")
+        return [(int(mem[i]), int(val[i])) for i in range(n.value)]
 
     def close(self) -> None:
         if self._h:

@@ -24,6 +24,7 @@
 #include "gf256.h"
 #include "rebuild_checked.h"
 #include "repair.h"
+#include "repair2.h"
 #include "stripe_map.h"
 
 using redset_hip::CellRef;
@@ -73,6 +74,9 @@ struct redset_hip_plan {
   redset_hip::RepairLaunch repair{};
   void* d_repair = nullptr;
   unsigned long long* d_repair_report = nullptr;
+  // two-error repair plans (REDSET_HIP_PLAN_RS_REPAIR2): their launch, over
+  // the same two allocations (the report has the pair counts at its end)
+  redset_hip::Repair2Launch repair2{};
   // checked rebuild plans (REDSET_HIP_PLAN_RS_REBUILD_CHECKED): the same
   redset_hip::CheckedLaunch checked{};
   void* d_checked = nullptr;
@@ -1224,6 +1228,150 @@ int redset_hip_plan_repair_report(const redset_hip_plan* plan, void* stream, red
   return REDSET_SUCCESS;
 }
 
+int redset_hip_rs_power_basis(const redset_hip_rs* rs, int chunk_id, unsigned char* alpha, unsigned char* u,
+                              unsigned char* winv) {
+  if (!rs || !alpha || !u || !winv) return fail("power_basis: null argument");
+  std::vector<uint8_t> a, uu, w;
+  if (int rc = redset_hip::rs_power_basis(rs, chunk_id, a, uu, w)) return rc;
+  std::memcpy(alpha, a.data(), a.size());
+  std::memcpy(u, uu.data(), uu.size());
+  std::memcpy(winv, w.data(), w.size());
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_locate_syndrome2(const redset_hip_rs* rs, int chunk_id, const unsigned char* syndrome,
+                                   int* members_out, unsigned char* values_out, int* count_out) {
+  if (!rs || !syndrome || !members_out || !values_out || !count_out) return fail("locate_syndrome2: null argument");
+  const int p = rs->ranks, e = rs->encoding, d = p - e;
+  *count_out = 0;
+  members_out[0] = members_out[1] = -1;
+  values_out[0] = values_out[1] = 0;
+  if (e != redset_hip::kRepair2E)
+    return fail("locate_syndrome2: encoding %d: the two-error repair is built for 4 parity rows", e);
+  int single = -1;
+  if (int rc = redset_hip_rs_locate_syndrome(rs, chunk_id, syndrome, &single)) return rc;
+  if (single >= 0) {
+    // its value: the parity row's own byte, or syndrome[j] / A[j][m] on any row with A[j][m] != 0
+    const int enc = redset_hip::encoding_id(p, e, single, chunk_id);
+    const redset_hip::Field& F = redset_hip::field();
+    unsigned char x = 0;
+    for (int j = 0; j < e && x == 0; ++j) {
+      const uint8_t a = enc >= p ? static_cast<uint8_t>(enc == p + j) : rs->mat[static_cast<size_t>(p + j) * p + single];
+      if (a) x = F.mul(syndrome[j], F.inv(a));
+    }
+    members_out[0] = single;
+    values_out[0] = x;
+    *count_out = 1;
+    return REDSET_SUCCESS;
+  }
+  bool any = false;
+  for (int j = 0; j < e; ++j) any = any || syndrome[j] != 0;
+  if (!any) return REDSET_SUCCESS;
+  int cols[2], n = 0;
+  uint8_t x[2];
+  if (int rc = redset_hip::locate_pair(rs, chunk_id, syndrome, cols, x, &n)) return rc;
+  if (n != 2) return REDSET_SUCCESS;
+  StripeMap m;
+  redset_hip::rs_verify_map(rs, chunk_id, m);
+  int mem[2];
+  for (int k = 0; k < 2; ++k) mem[k] = cols[k] < d ? m.in[static_cast<size_t>(cols[k])].rank : m.out[static_cast<size_t>(cols[k] - d)].rank;
+  const int lo = mem[0] < mem[1] ? 0 : 1;
+  members_out[0] = mem[lo], values_out[0] = x[lo];
+  members_out[1] = mem[1 - lo], values_out[1] = x[1 - lo];
+  *count_out = 2;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_plan_repair2(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                               size_t chunk_size, size_t stride, int nstripes, const int* stripes, int apply,
+                               redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  const int p = rs->ranks, e = rs->encoding, d = p - e;
+  if (e != redset_hip::kRepair2E)
+    return fail("plan_repair2: encoding %d: two wrong bytes per column need 4 parity rows (distance 5)", e);
+  if (!stripes) nstripes = p;
+  if (nstripes < 0 || nstripes > p) return fail("plan_repair2: %d stripes of a set of %d", nstripes, p);
+  std::vector<char> seen(static_cast<size_t>(p), 0);
+  std::vector<redset_hip::Repair2JobDesc> jobs(static_cast<size_t>(nstripes));
+  const SetLayout L{lofi, parity, stride};
+  for (int k = 0; k < nstripes; ++k) {
+    const int c = stripes ? stripes[k] : k;
+    if (c < 0 || c >= p) return fail("plan_repair2: stripe %d out of range", c);
+    if (seen[c]) return fail("plan_repair2: stripe %d listed twice", c);
+    seen[c] = 1;
+    StripeMap m;
+    redset_hip::rs_verify_map(rs, c, m);
+    std::vector<uint8_t*> data, par;
+    for (const CellRef& r : m.in) data.push_back(L.at(r));
+    for (const CellRef& r : m.out) par.push_back(L.at(r));
+    if (int rc = redset_hip::repair2_job(rs, c, data, par, k, jobs[static_cast<size_t>(k)])) return rc;
+  }
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = REDSET_HIP_PLAN_RS_REPAIR2;
+  plan->info.ranks = p;
+  plan->info.encoding = e;
+  plan->info.chunk_size = chunk_size;
+  plan->info.jobs = nstripes;
+  plan->info.launches = nstripes > 0 && chunk_size > 0 ? 2 : 1;
+  plan->info.bytes_read = static_cast<unsigned long long>(nstripes) * p * chunk_size;
+  redset_hip::Repair2Launch& R = plan->repair2;
+  R.njobs = nstripes;
+  R.d = d;
+  R.p = p;
+  R.apply = apply ? 1 : 0;
+  R.nbytes = chunk_size;
+  R.base = 0;
+  R.ncells = nstripes * p;
+  R.nstripes = nstripes;
+  const size_t words = 2 * static_cast<size_t>(R.ncells) + 3 * static_cast<size_t>(R.nstripes);
+  void* rp = nullptr;
+  int rc = hip_check(hipMalloc(&rp, std::max<size_t>(1, words) * sizeof(unsigned long long)), "hipMalloc(repair2 report)");
+  plan->d_repair_report = static_cast<unsigned long long*>(rp);
+  R.cell_report = plan->d_repair_report;
+  R.stripe_report = plan->d_repair_report + 2 * static_cast<size_t>(R.ncells);
+  R.pair_report = R.stripe_report + 2 * static_cast<size_t>(R.nstripes);
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::repair2_upload(jobs, d, &plan->d_repair, R)),
+                           "repair2 plan upload");
+  // a report read before the first execute says "nothing found"
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::launch_repair2_reset(R, nullptr)), "repair2 report reset");
+  rc = rc ? rc : hip_check(hipStreamSynchronize(nullptr), "repair2 report reset");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  R.blocks_per_job = redset_hip::repair_blocks_per_job(nstripes, chunk_size);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_repair2_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells, int ncells,
+                                   redset_hip_repair_stripe* stripes, int nstripes, unsigned long long* pair_columns) {
+  if (!plan) return fail("repair2_report: null plan");
+  if (plan->info.kind != REDSET_HIP_PLAN_RS_REPAIR2)
+    return fail("repair2_report: not a two-error repair plan (kind %d)", plan->info.kind);
+  const redset_hip::Repair2Launch& R = plan->repair2;
+  if (cells && ncells < R.ncells) return fail("repair2_report: room for %d cells, the plan reports %d", ncells, R.ncells);
+  if ((stripes || pair_columns) && nstripes < R.nstripes)
+    return fail("repair2_report: room for %d stripes, the plan reports %d", nstripes, R.nstripes);
+  const size_t nc = static_cast<size_t>(R.ncells), ns = static_cast<size_t>(R.nstripes);
+  std::vector<unsigned long long> raw(2 * nc + 3 * ns);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!raw.empty())
+    if (int rc = hip_check(hipMemcpyAsync(raw.data(), plan->d_repair_report, raw.size() * sizeof(unsigned long long),
+                                          hipMemcpyDeviceToHost, s),
+                           "repair2 report copy"))
+      return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "repair2 report sync")) return rc;
+  for (size_t i = 0; cells && i < nc; ++i) cells[i] = redset_hip_repair_cell{raw[i], raw[nc + i]};
+  for (size_t i = 0; stripes && i < ns; ++i) stripes[i] = redset_hip_repair_stripe{raw[2 * nc + i], raw[2 * nc + ns + i]};
+  for (size_t i = 0; pair_columns && i < ns; ++i) pair_columns[i] = raw[2 * nc + 2 * ns + i];
+  return REDSET_SUCCESS;
+}
+
 int redset_hip_rs_check_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
                                unsigned char* mat_out, int* cols_lost_out) {
   if (!rs || !mat_out) return fail("check_matrix: null argument");
@@ -1365,6 +1513,11 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
     if (int e = redset_hip::launch_repair_reset(plan->repair, stream))
       return hip_check(static_cast<hipError_t>(e), "repair report reset");
     return hip_check(static_cast<hipError_t>(redset_hip::launch_repair(plan->repair, stream)), "gf_repair launch");
+  }
+  if (plan->info.kind == REDSET_HIP_PLAN_RS_REPAIR2) {
+    if (int e = redset_hip::launch_repair2_reset(plan->repair2, stream))
+      return hip_check(static_cast<hipError_t>(e), "repair2 report reset");
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_repair2(plan->repair2, stream)), "gf_repair2 launch");
   }
   if (plan->info.kind == REDSET_HIP_PLAN_RS_REBUILD_CHECKED) {
     if (int e = redset_hip::launch_checked_reset(plan->checked, stream))

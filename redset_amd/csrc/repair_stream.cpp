@@ -17,6 +17,7 @@
 #include "codec_kernels.h"
 #include "redset_hip.h"
 #include "repair.h"
+#include "repair2.h"
 #include "stripe_map.h"
 
 using redset_hip::CellRef;
@@ -47,13 +48,13 @@ struct Staging {
   }
 };
 
-}  // namespace
-
-extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
-                                           size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
-                                           redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
-                                           redset_hip_repair_stripe* stripes, int nstripes_out,
-                                           redset_hip_repair_summary* summary) {
+// both levels of redset_hip_rs_repair*_stream; max_errors 2 launches
+// gf_repair2_kernel and adds up the pair columns
+int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
+                  int io_threads, const redset_hip_io* io, int apply, redset_hip_stream_stats* stats,
+                  redset_hip_repair_cell* cells, int ncells, redset_hip_repair_stripe* stripes, int nstripes_out,
+                  redset_hip_repair_summary* summary, int max_errors, unsigned long long* pair_columns_out) {
+  if (pair_columns_out) *pair_columns_out = 0;
   if (!rs) return fail("null rs state");
   if (!io || !io->read) return fail("null redset_hip_io");
   if (apply && !io->write) return fail("repair_stream: apply needs io->write");
@@ -62,6 +63,9 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
     return fail("repair_stream: encoding %d: one parity row locates nothing (rebuild the member a checksum names)", e);
   if (e > redset_hip::kMaxOut)
     return fail("repair_stream: encoding %d: repair is built for 2..%d parity rows", e, redset_hip::kMaxOut);
+  const bool two = max_errors == 2;
+  if (two && e != redset_hip::kRepair2E)
+    return fail("repair2_stream: encoding %d: two wrong bytes per column need 4 parity rows (distance 5)", e);
   if (nstripes <= 0) {
     first_stripe = 0;
     nstripes = p;
@@ -109,7 +113,7 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
   slice = (slice + 255) & ~static_cast<size_t>(255);
   Staging S;
   const size_t stage = static_cast<size_t>(p) * slice;
-  const size_t report_words = 2 * static_cast<size_t>(p) + 2;
+  const size_t report_words = 2 * static_cast<size_t>(p) + (two ? 3 : 2);
   if (int rc = hip_ok(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking), "hipStreamCreate")) return done(rc);
   if (int rc = hip_ok(hipHostMalloc(&S.host, stage, hipHostMallocDefault), "hipHostMalloc(repair staging)")) return done(rc);
   if (int rc = hip_ok(hipMalloc(&S.dev, stage), "hipMalloc(repair staging)")) return done(rc);
@@ -133,11 +137,19 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
     job[0].row = 0;
     redset_hip::RepairLaunch R;
     std::memset(&R, 0, sizeof(R));
+    redset_hip::Repair2Launch R2;
+    std::memset(&R2, 0, sizeof(R2));
     if (S.blob) (void) hipFree(S.blob);
     S.blob = nullptr;
-    if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::repair_upload(job, p - e, e, &S.blob, &R.jobs)),
-                        "repair job upload"))
+    if (two) {
+      std::vector<redset_hip::Repair2JobDesc> job2(1);
+      if (int rc = redset_hip::repair2_job(rs, c, job[0].data, job[0].parity, 0, job2[0])) return done(rc);
+      if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::repair2_upload(job2, p - e, &S.blob, R2)), "repair2 job upload"))
+        return done(rc);
+    } else if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::repair_upload(job, p - e, e, &S.blob, &R.jobs)),
+                               "repair job upload")) {
       return done(rc);
+    }
     R.njobs = 1;
     R.d = p - e;
     R.e = e;
@@ -147,6 +159,15 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
     R.ncells = p;
     R.stripe_report = R.cell_report + 2 * static_cast<size_t>(p);
     R.nstripes = 1;
+    R2.njobs = 1;
+    R2.d = p - e;
+    R2.p = p;
+    R2.apply = R.apply;
+    R2.cell_report = R.cell_report;
+    R2.ncells = p;
+    R2.stripe_report = R.stripe_report;
+    R2.pair_report = R.stripe_report + 2;
+    R2.nstripes = 1;
     for (size_t off = 0; off < chunk; off += slice) {
       const size_t len = std::min(slice, chunk - off);
       const double tr = now_s();
@@ -160,9 +181,17 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
       R.nbytes = len;
       R.base = off;
       R.blocks_per_job = redset_hip::repair_blocks_per_job(1, len);
-      if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::launch_repair_reset(R, S.stream)), "repair report reset"))
+      R2.nbytes = len;
+      R2.base = off;
+      R2.blocks_per_job = R.blocks_per_job;
+      if (int rc = hip_ok(static_cast<hipError_t>(two ? redset_hip::launch_repair2_reset(R2, S.stream)
+                                                      : redset_hip::launch_repair_reset(R, S.stream)),
+                          "repair report reset"))
         return done(rc);
-      if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::launch_repair(R, S.stream)), "gf_repair launch")) return done(rc);
+      if (int rc = hip_ok(static_cast<hipError_t>(two ? redset_hip::launch_repair2(R2, S.stream)
+                                                      : redset_hip::launch_repair(R, S.stream)),
+                          "gf_repair launch"))
+        return done(rc);
       if (int rc = hip_ok(hipMemcpyAsync(raw.data(), S.report, report_words * sizeof(unsigned long long),
                                          hipMemcpyDeviceToHost, S.stream),
                           "repair report copy"))
@@ -173,6 +202,7 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
       st.units += 1;
       const size_t k = static_cast<size_t>(c - lo);
       sum.unlocated_columns += raw[2 * static_cast<size_t>(p)];
+      if (two && pair_columns_out) *pair_columns_out += raw[2 * static_cast<size_t>(p) + 2];
       if (stripes && raw[2 * static_cast<size_t>(p)]) {
         stripes[k].unlocated_columns += raw[2 * static_cast<size_t>(p)];
         stripes[k].first_unlocated = std::min(stripes[k].first_unlocated, raw[2 * static_cast<size_t>(p) + 1]);
@@ -212,4 +242,24 @@ extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk
     }
   }
   return done(REDSET_SUCCESS);
+}
+
+}  // namespace
+
+extern "C" int redset_hip_rs_repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                           size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
+                                           redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
+                                           redset_hip_repair_stripe* stripes, int nstripes_out,
+                                           redset_hip_repair_summary* summary) {
+  return repair_stream(rs, chunk_size, first_stripe, nstripes, slice_bytes, io_threads, io, apply, stats, cells, ncells,
+                       stripes, nstripes_out, summary, 1, nullptr);
+}
+
+extern "C" int redset_hip_rs_repair2_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                            size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
+                                            redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
+                                            redset_hip_repair_stripe* stripes, int nstripes_out,
+                                            redset_hip_repair_summary* summary, unsigned long long* pair_columns_out) {
+  return repair_stream(rs, chunk_size, first_stripe, nstripes, slice_bytes, io_threads, io, apply, stats, cells, ncells,
+                       stripes, nstripes_out, summary, 2, pair_columns_out);
 }

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "gf256.h"
+#include "repair2.h"
 
 namespace redset_hip {
 
@@ -208,6 +209,128 @@ void locate_reduced(const CheckMatrix& X, const uint8_t* R, int* col_out, uint8_
     if (ok) found = m, val = x, ++matches;
   }
   if (matches == 1) *col_out = found, *value_out = val;
+}
+
+int rs_power_basis(const redset_hip_rs* rs, int c, std::vector<uint8_t>& alpha, std::vector<uint8_t>& u,
+                   std::vector<uint8_t>& winv) {
+  const int p = rs->ranks, e = rs->encoding, d = p - e, n = p + e;
+  const Field& F = field();
+  if (e != kRepair2E) return fail("power_basis: encoding %d: the two-error repair is built for 4 parity rows", e);
+  if (c < 0 || c >= p) return fail("power_basis: chunk id %d out of range", c);
+  if (n > 256) return fail("power_basis: %d points do not fit the field", n);
+  StripeMap m;
+  rs_verify_map(rs, c, m);
+  if (static_cast<int>(m.in.size()) != d || static_cast<int>(m.out.size()) != e)
+    return fail("power_basis: stripe %d has %zu data and %zu parity cells", c, m.in.size(), m.out.size());
+  alpha.assign(static_cast<size_t>(d + e), 0);
+  u.assign(static_cast<size_t>(d + e), 0);
+  winv.assign(static_cast<size_t>(e) * e, 0);
+  for (int i = 0; i < d + e; ++i) {
+    const int a = i < d ? m.in[static_cast<size_t>(i)].rank : p + (i - d);
+    uint8_t prod = 1;
+    for (int b = 0; b < n; ++b)
+      if (b != a) prod = F.mul(prod, static_cast<uint8_t>(a ^ b));
+    alpha[i] = static_cast<uint8_t>(a);
+    u[i] = F.inv(prod);
+  }
+  auto power_column = [&](int i, uint8_t* out) {  // u_i * alpha_i^t, 0^0 = 1
+    uint8_t v = u[i];
+    for (int t = 0; t < e; ++t, v = F.mul(v, alpha[i])) out[t] = v;
+  };
+  for (int j = 0; j < e; ++j) {
+    uint8_t col[kRepair2E];
+    power_column(d + j, col);
+    for (int t = 0; t < e; ++t) winv[static_cast<size_t>(t) * e + j] = col[t];
+  }
+  // the structure is checked, not assumed: W^-1 H[:, i] over every column
+  for (int i = 0; i < d + e; ++i) {
+    uint8_t want[kRepair2E];
+    power_column(i, want);
+    for (int t = 0; t < e; ++t) {
+      uint8_t got = 0;
+      for (int j = 0; j < e; ++j) {
+        const uint8_t h = i < d ? m.coef[static_cast<size_t>(j) * d + i] : static_cast<uint8_t>(j == i - d);
+        got ^= F.mul(winv[static_cast<size_t>(t) * e + j], h);
+      }
+      if (got != want[t])
+        return fail("power_basis: stripe %d column %d is not u * alpha^%d in the power basis (RS(%d,%d))", c, i, t, p, e);
+    }
+  }
+  return 0;
+}
+
+int locate_pair(const redset_hip_rs* rs, int c, const uint8_t* S, int* cols_out, uint8_t* values_out, int* count_out) {
+  const int e = kRepair2E;
+  const Field& F = field();
+  *count_out = 0;
+  std::vector<uint8_t> alpha, u, winv;
+  if (int rc = rs_power_basis(rs, c, alpha, u, winv)) return rc;
+  const int n = static_cast<int>(alpha.size()), d = n - e;
+  uint8_t s[kRepair2E] = {0, 0, 0, 0};
+  for (int t = 0; t < e; ++t)
+    for (int j = 0; j < e; ++j) s[t] ^= F.mul(winv[static_cast<size_t>(t) * e + j], S[j]);
+  auto div = [&](uint8_t a, uint8_t b) { return F.mul(a, F.inv(b)); };
+  const uint8_t D = F.mul(s[0], s[2]) ^ F.mul(s[1], s[1]);
+  if (D == 0) return 0;
+  const uint8_t sg2 = div(F.mul(s[2], s[2]) ^ F.mul(s[1], s[3]), D);
+  const uint8_t sg1 = div(F.mul(s[0], s[3]) ^ F.mul(s[1], s[2]), D);
+  int X[2], nroots = 0;
+  for (int z = 0; z < 256; ++z) {
+    const uint8_t zz = static_cast<uint8_t>(z);
+    if ((F.mul(zz, zz) ^ F.mul(sg1, zz) ^ sg2) != 0) continue;
+    if (nroots < 2) X[nroots] = z;
+    ++nroots;
+  }
+  if (nroots != 2) return 0;
+  int col[2];
+  for (int k = 0; k < 2; ++k) {
+    col[k] = -1;
+    for (int i = 0; i < n; ++i)
+      if (alpha[i] == X[k]) col[k] = i;
+    if (col[k] < 0) return 0;  // a shortened position or a point past p + e
+  }
+  const uint8_t y1 = div(F.mul(s[0], static_cast<uint8_t>(X[1])) ^ s[1], static_cast<uint8_t>(X[0] ^ X[1]));
+  const uint8_t y[2] = {y1, static_cast<uint8_t>(s[0] ^ y1)};
+  uint8_t x[2];
+  for (int k = 0; k < 2; ++k) {
+    x[k] = div(y[k], u[col[k]]);
+    if (x[k] == 0) return 0;
+  }
+  // the pair's own syndrome
+  StripeMap m;
+  rs_verify_map(rs, c, m);
+  for (int j = 0; j < e; ++j) {
+    uint8_t got = 0;
+    for (int k = 0; k < 2; ++k)
+      got ^= col[k] < d ? F.mul(m.coef[static_cast<size_t>(j) * d + col[k]], x[k])
+                        : static_cast<uint8_t>(j == col[k] - d ? x[k] : 0);
+    if (got != S[j]) return 0;
+  }
+  for (int k = 0; k < 2; ++k) cols_out[k] = col[k], values_out[k] = x[k];
+  *count_out = 2;
+  return 0;
+}
+
+int repair2_job(const redset_hip_rs* rs, int c, const std::vector<uint8_t*>& data, const std::vector<uint8_t*>& parity,
+                int row, Repair2JobDesc& out) {
+  const Field& F = field();
+  std::vector<uint8_t> u, winv;
+  if (int rc = rs_power_basis(rs, c, out.alpha, u, winv)) return rc;
+  StripeMap m;
+  rs_verify_map(rs, c, m);
+  if (data.size() != m.in.size() || parity.size() != m.out.size())
+    return fail("repair2: stripe %d takes %zu data and %zu parity cells", c, m.in.size(), m.out.size());
+  out.cells = RepairJobDesc();
+  out.cells.data = data;
+  out.cells.parity = parity;
+  out.cells.coef = m.coef;
+  for (const CellRef& r : m.in) out.cells.member.push_back(r.rank);
+  for (const CellRef& r : m.out) out.cells.member.push_back(r.rank);
+  out.cells.row = row;
+  out.invu.resize(u.size());
+  for (size_t i = 0; i < u.size(); ++i) out.invu[i] = F.inv(u[i]);
+  std::copy(winv.begin(), winv.end(), out.winv);
+  return 0;
 }
 
 namespace {

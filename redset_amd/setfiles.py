@@ -336,7 +336,7 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
 
 
 def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: bool = True,
-               checksums: bool = False) -> Dict:
+               checksums: bool = False, max_errors: int = 1) -> Dict:
     """Scrub one RS set on disk (2 <= e <= 4) and correct, in place, every
     byte column with one wrong byte (redset_amd.stream.rs_repair_stream):
     only the wrong bytes' cell slices are rewritten, and members each damaged
@@ -366,7 +366,11 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
     ``checksum_damaged`` lists what differs; any entry makes ``repaired``
     false -- the guard against e = 2's miscorrection of a column with two
     wrong bytes into a third member. Sidecars are not rewritten: a correct
-    repair restores the recorded bytes."""
+    repair restores the recorded bytes.
+    ``max_errors=2`` (e = 4 only, else ValueError): columns with two wrong
+    bytes are corrected too and counted in ``pair_columns``; a column with
+    three may then be miscorrected, as two are at e = 2, and ``checksums``
+    stays the arbiter."""
     f, reds, files, lost = _read_set(redundancy_files)
     p, k = f.ranks, f.encoding
     if lost:
@@ -377,6 +381,9 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
                          "(verify_set(checksums=True))")
     if k > 4:
         raise ValueError(f"RS set with {k} parity rows: repair is built for 2..4; rebuild_set the located member")
+    from .codec import check_max_errors
+
+    check_max_errors(max_errors, k)
     stored = _read_sidecar(reds, p, f.chunk) if checksums else None
     hsize = [f.header_size[r] for r in range(p)]
     codec = _codec("RS", p, k)
@@ -384,7 +391,8 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
     def run(writable, do_apply):
         io = stream.FileIO(files, reds, hsize, f.chunk, writable=writable)
         try:
-            return stream.rs_repair_stream(codec, f.chunk, io, slice_bytes=slice_bytes, apply=do_apply)
+            return stream.rs_repair_stream(codec, f.chunk, io, slice_bytes=slice_bytes, apply=do_apply,
+                                           max_errors=max_errors)
         finally:
             io.close()
 
@@ -398,6 +406,8 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
     for key in ("verify_mismatch_bytes", "corrected_bytes", "unlocated_columns", "remaining_mismatch_bytes",
                 "damaged_stripes", "repair_units", "cells_written"):
         out[key] = int(res[key])
+    if max_errors == 2:
+        out["pair_columns"] = int(res["pair_columns"])
     for c in range(p):
         if not res["corrected"][c].any() and not res["unlocated"][c]:
             continue
