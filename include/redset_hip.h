@@ -53,7 +53,8 @@ enum {
   REDSET_HIP_PLAN_CRC32 = 7,
   REDSET_HIP_PLAN_RS_REPAIR = 8,
   REDSET_HIP_PLAN_RS_REBUILD_CHECKED = 9,
-  REDSET_HIP_PLAN_RS_REPAIR2 = 10
+  REDSET_HIP_PLAN_RS_REPAIR2 = 10,
+  REDSET_HIP_PLAN_RS_REPAIR_WIDE = 11
 };
 
 typedef struct {
@@ -203,7 +204,8 @@ int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int
  * wrong bytes are written. Members each damaged at different offsets -- more
  * members than a rebuild has erasures for -- are repaired as long as every
  * byte column has at most one wrong byte. RS sets with 2 <= e <= 4 only: one
- * parity row (e = 1, XOR sets) locates nothing, and e > 4 is not built.
+ * parity row (e = 1, XOR sets) locates nothing, and 5 <= e <= 8 has its own
+ * entry points ("repair_wide" below).
  * Capability per e: a column with one wrong byte is always corrected; a
  * column with two wrong bytes is reported unlocated for e >= 3 and, for
  * e == 2 (distance 3), may be reported unlocated or MIScorrected into a third
@@ -289,6 +291,54 @@ int redset_hip_rs_plan_repair2(const redset_hip_rs* rs, unsigned char* const* lo
  * may be NULL): the columns of planned stripe k corrected as a pair. */
 int redset_hip_plan_repair2_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells, int ncells,
                                    redset_hip_repair_stripe* stripes, int nstripes, unsigned long long* pair_columns);
+
+/* ---- repair_wide (up to e/2 wrong bytes per column, 5 <= e <= 8) -------- */
+/*
+ * The same power basis with more rows: for 5 <= e <= 8 the rows
+ * u_i * alpha_i^k, k = 0 .. e-1, span the row space of H = [A | I], the e x e
+ * transform W^-1 turns the stored syndrome S into the power sums
+ * S'_k = sum_i y_i X_i^k over the wrong cells' points X_i (y_i = u_i x_i, x_i
+ * the error), and up to t = e / 2 (2, 3, 3, 4) wrong bytes of a column are
+ * found by Peterson-Gorenstein-Zierler, the full distance e + 1. The locator
+ * is written in the roots themselves: the point 0 is member 0's data cell.
+ *
+ * power_basis_wide (host): as redset_hip_rs_power_basis for any e in 5..8:
+ * alpha and u have d + e entries (data inputs ascending, then parity rows),
+ * winv is e x e row-major with winv * H[:, i] = u[i] * (1, alpha[i], ...,
+ * alpha[i]^(e-1)), checked for every one of the d + e columns before the call
+ * returns. e outside 5..8 and p + e > 256 (the points run out) are errors.
+ */
+int redset_hip_rs_power_basis_wide(const redset_hip_rs* rs, int chunk_id, unsigned char* alpha, unsigned char* u,
+                                   unsigned char* winv);
+/* The verdict on one byte column (host), max_errors in 1 .. e/2. S' = winv * S.
+ * For nu = 1 .. max_errors, in this order, the first nu is answered for which
+ * all of this holds: the nu x nu Hankel system sum_k sigma_k S'_(j+k) =
+ * S'_(j+nu), j = 0 .. nu-1, has a unique solution; that solution satisfies the
+ * same equation for every remaining j (j + nu < e); the locator
+ * z^nu ^ sigma_(nu-1) z^(nu-1) ^ ... ^ sigma_0 has exactly nu distinct roots
+ * among the points of this stripe's d + e cells; the values x_i = y_i / u_i of
+ * the Vandermonde system sum_i y_i X_i^k = S'_k, k < nu, are all nonzero; and
+ * the syndrome of that correction equals S. *count_out = nu, members_out
+ * ascending with values_out beside them (room for e/2 each); anything else,
+ * a clean column included, gives *count_out = 0. A column with more than
+ * max_errors wrong bytes is unlocated or, past the distance, MIScorrected into
+ * another set of at most max_errors cells: the member checksums arbitrate. */
+int redset_hip_rs_locate_syndrome_wide(const redset_hip_rs* rs, int chunk_id, const unsigned char* syndrome,
+                                       int max_errors, int* members_out, unsigned char* values_out, int* count_out);
+/* The repair plan with that verdict per column (gf_repair_wide_kernel<e>):
+ * contract, report and plan info as redset_hip_rs_plan_repair (kind 11), every
+ * byte of a correction counted, every correction applied only if its own
+ * syndrome equals the column's. e outside 5..8 and max_errors outside 1..e/2
+ * are REDSET_FAILURE, as is a shape whose tables do not fit a CU's LDS. */
+int redset_hip_rs_plan_repair_wide(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                                   size_t chunk_size, size_t cell_stride, int nstripes,
+                                   const int* stripes /* NULL: all p */, int apply, int max_errors, redset_hip_plan** out);
+/* As redset_hip_plan_repair_report, plus multi_columns[k * 3 + nu - 2]
+ * (3 * nstripes entries, may be NULL): the columns of planned stripe k
+ * corrected with nu = 2, 3, 4 wrong bytes. */
+int redset_hip_plan_repair_wide_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells,
+                                       int ncells, redset_hip_repair_stripe* stripes, int nstripes,
+                                       unsigned long long* multi_columns);
 
 /* ---- checked rebuild (errors-and-erasures decode) ---------------------- */
 /*
@@ -528,6 +578,14 @@ int redset_hip_rs_repair2_stream(const redset_hip_rs* rs, size_t chunk_size, int
                                  redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
                                  redset_hip_repair_stripe* stripes, int nstripes_out, redset_hip_repair_summary* summary,
                                  unsigned long long* pair_columns_out);
+/* The same flow with the repair_wide kernel (5 <= e <= 8, max_errors in
+ * 1 .. e/2, see "repair_wide" above); multi_columns_out (3 entries, may be
+ * NULL) = the columns corrected with 2, 3 and 4 wrong bytes. */
+int redset_hip_rs_repair_wide_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                     size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
+                                     int max_errors, redset_hip_stream_stats* stats, redset_hip_repair_cell* cells,
+                                     int ncells, redset_hip_repair_stripe* stripes, int nstripes_out,
+                                     redset_hip_repair_summary* summary, unsigned long long* multi_columns_out);
 
 /* Checked rebuild of a host-resident set (memory or files, see "checked
  * rebuild" above). For every stripe of the call and every slice,

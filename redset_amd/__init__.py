@@ -15,6 +15,7 @@ from .codec import (  # noqa: F401
     RebuildCheckedPlan,
     Repair2Plan,
     RepairPlan,
+    RepairWidePlan,
     SetLayout,
     VerifyPlan,
     gf_combine,
@@ -29,6 +30,6 @@ from .codec import (  # noqa: F401
 )
 from .checksum import Crc32Plan, crc32_combine  # noqa: F401
 from .setfiles import rebuild_set, repair_set, verify_set  # noqa: F401
-from .stream import rs_rebuild_checked_stream, rs_repair_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
+from .stream import rs_rebuild_checked_stream, rs_repair_stream, rs_repair_wide_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
 
 __version__ = "0.1.0"

@@ -138,6 +138,19 @@ def check_max_errors(max_errors: int, encoding: int) -> None:
                          "distance 5, that is e = 4")
 
 
+def wide_max_errors(max_errors: Optional[int], encoding: int) -> int:
+    """The correction levels of the wide repair (5 <= e <= 8): 1 .. e // 2,
+    None meaning e // 2."""
+    if not 5 <= encoding <= 8:
+        raise ValueError(f"wide repair on a set with {encoding} parity rows: it is built for 5..8")
+    t = encoding // 2
+    if max_errors is None:
+        return t
+    if not 1 <= max_errors <= t:
+        raise ValueError(f"max_errors={max_errors}: {encoding} parity rows correct 1..{t} wrong bytes per column")
+    return int(max_errors)
+
+
 def repair_arrays(cells, stripes, n: int, p: int):
     """(corrected[n, p], first[n, p], unlocated[n], first_unlocated[n]) of
     redset_hip_repair_cell / redset_hip_repair_stripe arrays."""
@@ -185,6 +198,25 @@ class Repair2Plan(Plan):
         _lib.check(_lib.load().redset_hip_plan_repair2_report(self._h, _stream_handle(stream), cells, n * p,
                                                               stripes, n, pairs), "plan_repair2_report")
         return repair_arrays(cells, stripes, n, p) + (np.array(pairs[:n], dtype=np.uint64),)
+
+
+class RepairWidePlan(Plan):
+    """A wide repair plan (RS sets with 5 <= e <= 8): columns with up to
+    ``max_errors`` <= e // 2 wrong bytes are corrected (include/redset_hip.h,
+    "repair_wide")."""
+
+    def report(self, stream=None):
+        """RepairPlan.report's four arrays -- every byte of a correction is
+        counted -- and ``multi_columns`` [n, 3]: the columns of each planned
+        stripe corrected with 2, 3 and 4 wrong bytes. Waits for the work on
+        ``stream``."""
+        n, p = int(self.info.jobs), int(self.info.ranks)
+        cells = (_lib.RepairCell * max(1, n * p))()
+        stripes = (_lib.RepairStripe * max(1, n))()
+        multi = (ctypes.c_ulonglong * max(1, 3 * n))()
+        _lib.check(_lib.load().redset_hip_plan_repair_wide_report(self._h, _stream_handle(stream), cells, n * p,
+                                                                  stripes, n, multi), "plan_repair_wide_report")
+        return repair_arrays(cells, stripes, n, p) + (np.array(multi[:3 * n], dtype=np.uint64).reshape(n, 3),)
 
 
 class RebuildCheckedPlan(Plan):
@@ -307,6 +339,25 @@ class RSCodec:
         )
         return RepairPlan(h, (self, lofi, parity))
 
+    def plan_repair_wide(self, lofi, parity, chunk_size: int, cell_stride: Optional[int] = None,
+                         stripes: Optional[Sequence[int]] = None, apply: bool = True,
+                         max_errors: Optional[int] = None) -> "RepairWidePlan":
+        """plan_repair for sets with 5 <= e <= 8: every byte column with up
+        to ``max_errors`` wrong bytes (1 .. e // 2; None: e // 2) is
+        corrected. Other e, or max_errors out of range: ValueError."""
+        max_errors = wide_max_errors(max_errors, self.encoding)
+        stride = chunk_size if cell_stride is None else cell_stride
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        n = 0 if stripes is None else len(stripes)
+        arr = None if stripes is None else (c_int * max(1, n))(*[int(c) for c in stripes])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_repair_wide(self._h, a, b, chunk_size, stride, n, arr, int(bool(apply)),
+                                                       max_errors, ctypes.byref(h)),
+            "rs_plan_repair_wide",
+        )
+        return RepairWidePlan(h, (self, lofi, parity))
+
     def plan_rebuild_checked(self, rebuild_ranks: Sequence[int], lofi, parity, chunk_size: int,
                              cell_stride: Optional[int] = None, fix_survivors: bool = False) -> "RebuildCheckedPlan":
         """Rebuild the lost members and check the survivors against the spare
@@ -383,6 +434,30 @@ class RSCodec:
         mem, val, n = (c_int * 2)(), (c_ubyte * 2)(), c_int(0)
         _lib.check(_lib.load().redset_hip_rs_locate_syndrome2(self._h, chunk_id, syn, mem, val, ctypes.byref(n)),
                    "rs_locate_syndrome2")
+        return [(int(mem[i]), int(val[i])) for i in range(n.value)]
+
+    def power_basis_wide(self, chunk_id: int):
+        """power_basis for 5 <= e <= 8: ``(alpha, u, winv)`` with
+        winv @ H[:, i] = u[i] * alpha[i]^k, k = 0 .. e - 1
+        (include/redset_hip.h redset_hip_rs_power_basis_wide)."""
+        n, e = self.ranks, self.encoding
+        alpha, u, winv = (c_ubyte * n)(), (c_ubyte * n)(), (c_ubyte * (e * e))()
+        _lib.check(_lib.load().redset_hip_rs_power_basis_wide(self._h, chunk_id, alpha, u, winv), "rs_power_basis_wide")
+        as_np = lambda b: np.frombuffer(bytes(b), dtype=np.uint8).copy()  # noqa: E731
+        return as_np(alpha), as_np(u), as_np(winv).reshape(e, e)
+
+    def locate_syndrome_wide(self, chunk_id: int, syndrome, max_errors: Optional[int] = None):
+        """``[(member, value), ...]``: the up to ``max_errors`` (None: e // 2)
+        members, ascending, whose wrong bytes give this syndrome column in
+        stripe chunk_id, with the error values; empty when clean or unlocated
+        (5 <= e <= 8; include/redset_hip.h redset_hip_rs_locate_syndrome_wide)."""
+        e = self.encoding
+        t = max(1, e // 2)
+        syn = (c_ubyte * max(8, e))(*[int(x) for x in syndrome])
+        mem, val, n = (c_int * t)(), (c_ubyte * t)(), c_int(0)
+        _lib.check(_lib.load().redset_hip_rs_locate_syndrome_wide(
+            self._h, chunk_id, syn, t if max_errors is None else int(max_errors), mem, val, ctypes.byref(n)),
+            "rs_locate_syndrome_wide")
         return [(int(mem[i]), int(val[i])) for i in range(n.value)]
 
     def close(self) -> None:

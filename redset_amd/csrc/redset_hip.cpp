@@ -25,6 +25,7 @@
 #include "rebuild_checked.h"
 #include "repair.h"
 #include "repair2.h"
+#include "repair_wide.h"
 #include "stripe_map.h"
 
 using redset_hip::CellRef;
@@ -77,6 +78,9 @@ struct redset_hip_plan {
   // two-error repair plans (REDSET_HIP_PLAN_RS_REPAIR2): their launch, over
   // the same two allocations (the report has the pair counts at its end)
   redset_hip::Repair2Launch repair2{};
+  // wide repair plans (REDSET_HIP_PLAN_RS_REPAIR_WIDE): the same, the nu
+  // histogram at the report's end
+  redset_hip::RepairWideLaunch repair_wide{};
   // checked rebuild plans (REDSET_HIP_PLAN_RS_REBUILD_CHECKED): the same
   redset_hip::CheckedLaunch checked{};
   void* d_checked = nullptr;
@@ -1372,6 +1376,145 @@ int redset_hip_plan_repair2_report(const redset_hip_plan* plan, void* stream, re
   return REDSET_SUCCESS;
 }
 
+int redset_hip_rs_power_basis_wide(const redset_hip_rs* rs, int chunk_id, unsigned char* alpha, unsigned char* u,
+                                   unsigned char* winv) {
+  if (!rs || !alpha || !u || !winv) return fail("power_basis_wide: null argument");
+  std::vector<uint8_t> a, uu, w;
+  if (int rc = redset_hip::rs_power_basis_wide(rs, chunk_id, a, uu, w)) return rc;
+  std::memcpy(alpha, a.data(), a.size());
+  std::memcpy(u, uu.data(), uu.size());
+  std::memcpy(winv, w.data(), w.size());
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_locate_syndrome_wide(const redset_hip_rs* rs, int chunk_id, const unsigned char* syndrome,
+                                       int max_errors, int* members_out, unsigned char* values_out, int* count_out) {
+  if (!rs || !syndrome || !members_out || !values_out || !count_out) return fail("locate_syndrome_wide: null argument");
+  const int p = rs->ranks, e = rs->encoding, d = p - e;
+  *count_out = 0;
+  if (e < redset_hip::kWideMinE || e > redset_hip::kWideMaxE)
+    return fail("locate_syndrome_wide: encoding %d: the wide repair is built for %d..%d parity rows", e,
+                redset_hip::kWideMinE, redset_hip::kWideMaxE);
+  int cols[redset_hip::kWideMaxT], n = 0;
+  uint8_t x[redset_hip::kWideMaxT];
+  if (int rc = redset_hip::locate_wide(rs, chunk_id, syndrome, max_errors, cols, x, &n)) return rc;
+  StripeMap m;
+  redset_hip::rs_verify_map(rs, chunk_id, m);
+  std::vector<std::pair<int, uint8_t>> found;
+  for (int k = 0; k < n; ++k)
+    found.emplace_back(cols[k] < d ? m.in[static_cast<size_t>(cols[k])].rank : m.out[static_cast<size_t>(cols[k] - d)].rank,
+                       x[k]);
+  std::sort(found.begin(), found.end());
+  for (int k = 0; k < n; ++k) members_out[k] = found[static_cast<size_t>(k)].first, values_out[k] = found[static_cast<size_t>(k)].second;
+  *count_out = n;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_plan_repair_wide(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                                   size_t chunk_size, size_t stride, int nstripes, const int* stripes, int apply,
+                                   int max_errors, redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  const int p = rs->ranks, e = rs->encoding, d = p - e;
+  if (e < redset_hip::kWideMinE || e > redset_hip::kWideMaxE)
+    return fail("plan_repair_wide: encoding %d: the wide repair is built for %d..%d parity rows", e,
+                redset_hip::kWideMinE, redset_hip::kWideMaxE);
+  if (max_errors < 1 || max_errors > e / 2)
+    return fail("plan_repair_wide: max_errors %d: %d parity rows correct 1..%d wrong bytes per column", max_errors, e,
+                e / 2);
+  if (redset_hip::repair_wide_lds_bytes(d, e) > redset_hip::kWideLdsLimit)
+    return fail("plan_repair_wide: RS(%d,%d) takes %zu bytes of LDS a block, a CU has %zu", p, e,
+                redset_hip::repair_wide_lds_bytes(d, e), redset_hip::kWideLdsLimit);
+  if (!stripes) nstripes = p;
+  if (nstripes < 0 || nstripes > p) return fail("plan_repair_wide: %d stripes of a set of %d", nstripes, p);
+  std::vector<char> seen(static_cast<size_t>(p), 0);
+  std::vector<redset_hip::RepairWideJobDesc> jobs(static_cast<size_t>(nstripes));
+  const SetLayout L{lofi, parity, stride};
+  for (int k = 0; k < nstripes; ++k) {
+    const int c = stripes ? stripes[k] : k;
+    if (c < 0 || c >= p) return fail("plan_repair_wide: stripe %d out of range", c);
+    if (seen[c]) return fail("plan_repair_wide: stripe %d listed twice", c);
+    seen[c] = 1;
+    StripeMap m;
+    redset_hip::rs_verify_map(rs, c, m);
+    std::vector<uint8_t*> data, par;
+    for (const CellRef& r : m.in) data.push_back(L.at(r));
+    for (const CellRef& r : m.out) par.push_back(L.at(r));
+    if (int rc = redset_hip::repair_wide_job(rs, c, data, par, k, jobs[static_cast<size_t>(k)])) return rc;
+  }
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = REDSET_HIP_PLAN_RS_REPAIR_WIDE;
+  plan->info.ranks = p;
+  plan->info.encoding = e;
+  plan->info.chunk_size = chunk_size;
+  plan->info.jobs = nstripes;
+  plan->info.launches = nstripes > 0 && chunk_size > 0 ? 2 : 1;
+  plan->info.bytes_read = static_cast<unsigned long long>(nstripes) * p * chunk_size;
+  redset_hip::RepairWideLaunch& R = plan->repair_wide;
+  R.njobs = nstripes;
+  R.d = d;
+  R.e = e;
+  R.p = p;
+  R.apply = apply ? 1 : 0;
+  R.max_errors = max_errors;
+  R.nbytes = chunk_size;
+  R.base = 0;
+  R.ncells = nstripes * p;
+  R.nstripes = nstripes;
+  const size_t nh = redset_hip::kWideMaxT - 1;
+  const size_t words = 2 * static_cast<size_t>(R.ncells) + (2 + nh) * static_cast<size_t>(R.nstripes);
+  void* rp = nullptr;
+  int rc = hip_check(hipMalloc(&rp, std::max<size_t>(1, words) * sizeof(unsigned long long)),
+                     "hipMalloc(repair_wide report)");
+  plan->d_repair_report = static_cast<unsigned long long*>(rp);
+  R.cell_report = plan->d_repair_report;
+  R.stripe_report = plan->d_repair_report + 2 * static_cast<size_t>(R.ncells);
+  R.multi_report = R.stripe_report + 2 * static_cast<size_t>(R.nstripes);
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::repair_wide_prepare(d, e)), "repair_wide LDS attribute");
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::repair_wide_upload(jobs, d, e, &plan->d_repair, R)),
+                           "repair_wide plan upload");
+  // a report read before the first execute says "nothing found"
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::launch_repair_wide_reset(R, nullptr)),
+                           "repair_wide report reset");
+  rc = rc ? rc : hip_check(hipStreamSynchronize(nullptr), "repair_wide report reset");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  R.blocks_per_job = redset_hip::repair_blocks_per_job(nstripes, chunk_size);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_repair_wide_report(const redset_hip_plan* plan, void* stream, redset_hip_repair_cell* cells,
+                                       int ncells, redset_hip_repair_stripe* stripes, int nstripes,
+                                       unsigned long long* multi_columns) {
+  if (!plan) return fail("repair_wide_report: null plan");
+  if (plan->info.kind != REDSET_HIP_PLAN_RS_REPAIR_WIDE)
+    return fail("repair_wide_report: not a wide repair plan (kind %d)", plan->info.kind);
+  const redset_hip::RepairWideLaunch& R = plan->repair_wide;
+  if (cells && ncells < R.ncells)
+    return fail("repair_wide_report: room for %d cells, the plan reports %d", ncells, R.ncells);
+  if ((stripes || multi_columns) && nstripes < R.nstripes)
+    return fail("repair_wide_report: room for %d stripes, the plan reports %d", nstripes, R.nstripes);
+  const size_t nc = static_cast<size_t>(R.ncells), ns = static_cast<size_t>(R.nstripes), nh = redset_hip::kWideMaxT - 1;
+  std::vector<unsigned long long> raw(2 * nc + (2 + nh) * ns);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!raw.empty())
+    if (int rc = hip_check(hipMemcpyAsync(raw.data(), plan->d_repair_report, raw.size() * sizeof(unsigned long long),
+                                          hipMemcpyDeviceToHost, s),
+                           "repair_wide report copy"))
+      return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "repair_wide report sync")) return rc;
+  for (size_t i = 0; cells && i < nc; ++i) cells[i] = redset_hip_repair_cell{raw[i], raw[nc + i]};
+  for (size_t i = 0; stripes && i < ns; ++i) stripes[i] = redset_hip_repair_stripe{raw[2 * nc + i], raw[2 * nc + ns + i]};
+  for (size_t i = 0; multi_columns && i < nh * ns; ++i) multi_columns[i] = raw[2 * nc + 2 * ns + i];
+  return REDSET_SUCCESS;
+}
+
 int redset_hip_rs_check_matrix(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
                                unsigned char* mat_out, int* cols_lost_out) {
   if (!rs || !mat_out) return fail("check_matrix: null argument");
@@ -1518,6 +1661,12 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
     if (int e = redset_hip::launch_repair2_reset(plan->repair2, stream))
       return hip_check(static_cast<hipError_t>(e), "repair2 report reset");
     return hip_check(static_cast<hipError_t>(redset_hip::launch_repair2(plan->repair2, stream)), "gf_repair2 launch");
+  }
+  if (plan->info.kind == REDSET_HIP_PLAN_RS_REPAIR_WIDE) {
+    if (int e = redset_hip::launch_repair_wide_reset(plan->repair_wide, stream))
+      return hip_check(static_cast<hipError_t>(e), "repair_wide report reset");
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_repair_wide(plan->repair_wide, stream)),
+                     "gf_repair_wide launch");
   }
   if (plan->info.kind == REDSET_HIP_PLAN_RS_REBUILD_CHECKED) {
     if (int e = redset_hip::launch_checked_reset(plan->checked, stream))

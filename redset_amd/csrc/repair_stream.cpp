@@ -18,6 +18,7 @@
 #include "redset_hip.h"
 #include "repair.h"
 #include "repair2.h"
+#include "repair_wide.h"
 #include "stripe_map.h"
 
 using redset_hip::CellRef;
@@ -48,22 +49,32 @@ struct Staging {
   }
 };
 
-// both levels of redset_hip_rs_repair*_stream; max_errors 2 launches
-// gf_repair2_kernel and adds up the pair columns
+// the levels of redset_hip_rs_repair*_stream; max_errors 2 launches
+// gf_repair2_kernel and adds up the pair columns; `wide` launches
+// gf_repair_wide_kernel (5 <= e <= 8) with max_errors 1..e/2 and adds up the
+// three-entry nu histogram in pair_columns_out
 int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
                   int io_threads, const redset_hip_io* io, int apply, redset_hip_stream_stats* stats,
                   redset_hip_repair_cell* cells, int ncells, redset_hip_repair_stripe* stripes, int nstripes_out,
-                  redset_hip_repair_summary* summary, int max_errors, unsigned long long* pair_columns_out) {
-  if (pair_columns_out) *pair_columns_out = 0;
+                  redset_hip_repair_summary* summary, int max_errors, unsigned long long* pair_columns_out,
+                  bool wide = false) {
+  const size_t nextra = wide ? redset_hip::kWideMaxT - 1 : 1;
+  for (size_t i = 0; pair_columns_out && i < nextra; ++i) pair_columns_out[i] = 0;
   if (!rs) return fail("null rs state");
   if (!io || !io->read) return fail("null redset_hip_io");
   if (apply && !io->write) return fail("repair_stream: apply needs io->write");
   const int p = rs->ranks, e = rs->encoding;
   if (e < 2)
     return fail("repair_stream: encoding %d: one parity row locates nothing (rebuild the member a checksum names)", e);
-  if (e > redset_hip::kMaxOut)
+  if (wide && (e < redset_hip::kWideMinE || e > redset_hip::kWideMaxE))
+    return fail("repair_wide_stream: encoding %d: the wide repair is built for %d..%d parity rows", e,
+                redset_hip::kWideMinE, redset_hip::kWideMaxE);
+  if (wide && (max_errors < 1 || max_errors > e / 2))
+    return fail("repair_wide_stream: max_errors %d: %d parity rows correct 1..%d wrong bytes per column", max_errors, e,
+                e / 2);
+  if (!wide && e > redset_hip::kMaxOut)
     return fail("repair_stream: encoding %d: repair is built for 2..%d parity rows", e, redset_hip::kMaxOut);
-  const bool two = max_errors == 2;
+  const bool two = !wide && max_errors == 2;
   if (two && e != redset_hip::kRepair2E)
     return fail("repair2_stream: encoding %d: two wrong bytes per column need 4 parity rows (distance 5)", e);
   if (nstripes <= 0) {
@@ -113,7 +124,10 @@ int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, 
   slice = (slice + 255) & ~static_cast<size_t>(255);
   Staging S;
   const size_t stage = static_cast<size_t>(p) * slice;
-  const size_t report_words = 2 * static_cast<size_t>(p) + (two ? 3 : 2);
+  const size_t report_words = 2 * static_cast<size_t>(p) + (wide ? 2 + nextra : two ? 3 : 2);
+  if (wide)
+    if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::repair_wide_prepare(p - e, e)), "repair_wide LDS attribute"))
+      return done(rc);
   if (int rc = hip_ok(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking), "hipStreamCreate")) return done(rc);
   if (int rc = hip_ok(hipHostMalloc(&S.host, stage, hipHostMallocDefault), "hipHostMalloc(repair staging)")) return done(rc);
   if (int rc = hip_ok(hipMalloc(&S.dev, stage), "hipMalloc(repair staging)")) return done(rc);
@@ -141,7 +155,15 @@ int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, 
     std::memset(&R2, 0, sizeof(R2));
     if (S.blob) (void) hipFree(S.blob);
     S.blob = nullptr;
-    if (two) {
+    redset_hip::RepairWideLaunch RW;
+    std::memset(&RW, 0, sizeof(RW));
+    if (wide) {
+      std::vector<redset_hip::RepairWideJobDesc> jobw(1);
+      if (int rc = redset_hip::repair_wide_job(rs, c, job[0].data, job[0].parity, 0, jobw[0])) return done(rc);
+      if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::repair_wide_upload(jobw, p - e, e, &S.blob, RW)),
+                          "repair_wide job upload"))
+        return done(rc);
+    } else if (two) {
       std::vector<redset_hip::Repair2JobDesc> job2(1);
       if (int rc = redset_hip::repair2_job(rs, c, job[0].data, job[0].parity, 0, job2[0])) return done(rc);
       if (int rc = hip_ok(static_cast<hipError_t>(redset_hip::repair2_upload(job2, p - e, &S.blob, R2)), "repair2 job upload"))
@@ -168,6 +190,17 @@ int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, 
     R2.stripe_report = R.stripe_report;
     R2.pair_report = R.stripe_report + 2;
     R2.nstripes = 1;
+    RW.njobs = 1;
+    RW.d = p - e;
+    RW.e = e;
+    RW.p = p;
+    RW.apply = R.apply;
+    RW.max_errors = max_errors;
+    RW.cell_report = R.cell_report;
+    RW.ncells = p;
+    RW.stripe_report = R.stripe_report;
+    RW.multi_report = R.stripe_report + 2;
+    RW.nstripes = 1;
     for (size_t off = 0; off < chunk; off += slice) {
       const size_t len = std::min(slice, chunk - off);
       const double tr = now_s();
@@ -184,12 +217,17 @@ int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, 
       R2.nbytes = len;
       R2.base = off;
       R2.blocks_per_job = R.blocks_per_job;
-      if (int rc = hip_ok(static_cast<hipError_t>(two ? redset_hip::launch_repair2_reset(R2, S.stream)
-                                                      : redset_hip::launch_repair_reset(R, S.stream)),
+      RW.nbytes = len;
+      RW.base = off;
+      RW.blocks_per_job = R.blocks_per_job;
+      if (int rc = hip_ok(static_cast<hipError_t>(wide  ? redset_hip::launch_repair_wide_reset(RW, S.stream)
+                                                  : two ? redset_hip::launch_repair2_reset(R2, S.stream)
+                                                        : redset_hip::launch_repair_reset(R, S.stream)),
                           "repair report reset"))
         return done(rc);
-      if (int rc = hip_ok(static_cast<hipError_t>(two ? redset_hip::launch_repair2(R2, S.stream)
-                                                      : redset_hip::launch_repair(R, S.stream)),
+      if (int rc = hip_ok(static_cast<hipError_t>(wide  ? redset_hip::launch_repair_wide(RW, S.stream)
+                                                  : two ? redset_hip::launch_repair2(R2, S.stream)
+                                                        : redset_hip::launch_repair(R, S.stream)),
                           "gf_repair launch"))
         return done(rc);
       if (int rc = hip_ok(hipMemcpyAsync(raw.data(), S.report, report_words * sizeof(unsigned long long),
@@ -202,7 +240,8 @@ int repair_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, 
       st.units += 1;
       const size_t k = static_cast<size_t>(c - lo);
       sum.unlocated_columns += raw[2 * static_cast<size_t>(p)];
-      if (two && pair_columns_out) *pair_columns_out += raw[2 * static_cast<size_t>(p) + 2];
+      if ((two || wide) && pair_columns_out)
+        for (size_t i = 0; i < nextra; ++i) pair_columns_out[i] += raw[2 * static_cast<size_t>(p) + 2 + i];
       if (stripes && raw[2 * static_cast<size_t>(p)]) {
         stripes[k].unlocated_columns += raw[2 * static_cast<size_t>(p)];
         stripes[k].first_unlocated = std::min(stripes[k].first_unlocated, raw[2 * static_cast<size_t>(p) + 1]);
@@ -262,4 +301,14 @@ extern "C" int redset_hip_rs_repair2_stream(const redset_hip_rs* rs, size_t chun
                                             redset_hip_repair_summary* summary, unsigned long long* pair_columns_out) {
   return repair_stream(rs, chunk_size, first_stripe, nstripes, slice_bytes, io_threads, io, apply, stats, cells, ncells,
                        stripes, nstripes_out, summary, 2, pair_columns_out);
+}
+
+extern "C" int redset_hip_rs_repair_wide_stream(const redset_hip_rs* rs, size_t chunk_size, int first_stripe, int nstripes,
+                                                size_t slice_bytes, int io_threads, const redset_hip_io* io, int apply,
+                                                int max_errors, redset_hip_stream_stats* stats,
+                                                redset_hip_repair_cell* cells, int ncells,
+                                                redset_hip_repair_stripe* stripes, int nstripes_out,
+                                                redset_hip_repair_summary* summary, unsigned long long* multi_columns_out) {
+  return repair_stream(rs, chunk_size, first_stripe, nstripes, slice_bytes, io_threads, io, apply, stats, cells, ncells,
+                       stripes, nstripes_out, summary, max_errors, multi_columns_out, true);
 }

@@ -8,6 +8,7 @@
 
 #include "gf256.h"
 #include "repair2.h"
+#include "repair_wide.h"
 
 namespace redset_hip {
 
@@ -330,6 +331,170 @@ int repair2_job(const redset_hip_rs* rs, int c, const std::vector<uint8_t*>& dat
   out.invu.resize(u.size());
   for (size_t i = 0; i < u.size(); ++i) out.invu[i] = F.inv(u[i]);
   std::copy(winv.begin(), winv.end(), out.winv);
+  return 0;
+}
+
+int rs_power_basis_wide(const redset_hip_rs* rs, int c, std::vector<uint8_t>& alpha, std::vector<uint8_t>& u,
+                        std::vector<uint8_t>& winv) {
+  const int p = rs->ranks, e = rs->encoding, d = p - e, n = p + e;
+  const Field& F = field();
+  if (e < kWideMinE || e > kWideMaxE)
+    return fail("power_basis_wide: encoding %d: the wide repair is built for %d..%d parity rows", e, kWideMinE, kWideMaxE);
+  if (c < 0 || c >= p) return fail("power_basis_wide: chunk id %d out of range", c);
+  if (n > 256) return fail("power_basis_wide: p + e = %d points do not fit the field (p + e > 256)", n);
+  StripeMap m;
+  rs_verify_map(rs, c, m);
+  if (static_cast<int>(m.in.size()) != d || static_cast<int>(m.out.size()) != e)
+    return fail("power_basis_wide: stripe %d has %zu data and %zu parity cells", c, m.in.size(), m.out.size());
+  alpha.assign(static_cast<size_t>(d + e), 0);
+  u.assign(static_cast<size_t>(d + e), 0);
+  winv.assign(static_cast<size_t>(e) * e, 0);
+  for (int i = 0; i < d + e; ++i) {
+    const int a = i < d ? m.in[static_cast<size_t>(i)].rank : p + (i - d);
+    uint8_t prod = 1;
+    for (int b = 0; b < n; ++b)
+      if (b != a) prod = F.mul(prod, static_cast<uint8_t>(a ^ b));
+    alpha[i] = static_cast<uint8_t>(a);
+    u[i] = F.inv(prod);
+  }
+  auto power_column = [&](int i, uint8_t* out) {  // u_i * alpha_i^k, 0^0 = 1
+    uint8_t v = u[i];
+    for (int k = 0; k < e; ++k, v = F.mul(v, alpha[i])) out[k] = v;
+  };
+  for (int j = 0; j < e; ++j) {
+    uint8_t col[kWideMaxE];
+    power_column(d + j, col);
+    for (int k = 0; k < e; ++k) winv[static_cast<size_t>(k) * e + j] = col[k];
+  }
+  // the structure is checked, not assumed: W^-1 H[:, i] over every column
+  for (int i = 0; i < d + e; ++i) {
+    uint8_t want[kWideMaxE];
+    power_column(i, want);
+    for (int k = 0; k < e; ++k) {
+      uint8_t got = 0;
+      for (int j = 0; j < e; ++j) {
+        const uint8_t h = i < d ? m.coef[static_cast<size_t>(j) * d + i] : static_cast<uint8_t>(j == i - d);
+        got ^= F.mul(winv[static_cast<size_t>(k) * e + j], h);
+      }
+      if (got != want[k])
+        return fail("power_basis_wide: stripe %d column %d is not u * alpha^%d in the power basis (RS(%d,%d))", c, i, k, p,
+                    e);
+    }
+  }
+  return 0;
+}
+
+int locate_wide(const redset_hip_rs* rs, int c, const uint8_t* S, int max_errors, int* cols_out, uint8_t* values_out,
+                int* count_out) {
+  const Field& F = field();
+  *count_out = 0;
+  std::vector<uint8_t> alpha, u, winv;
+  if (int rc = rs_power_basis_wide(rs, c, alpha, u, winv)) return rc;
+  const int e = rs->encoding, n = static_cast<int>(alpha.size()), d = n - e, t = e / 2;
+  if (max_errors < 1 || max_errors > t)
+    return fail("locate_syndrome_wide: max_errors %d: %d parity rows correct 1..%d wrong bytes per column", max_errors, e, t);
+  bool any = false;
+  for (int j = 0; j < e; ++j) any = any || S[j] != 0;
+  if (!any) return 0;
+  uint8_t s[kWideMaxE] = {0};
+  for (int k = 0; k < e; ++k)
+    for (int j = 0; j < e; ++j) s[k] ^= F.mul(winv[static_cast<size_t>(k) * e + j], S[j]);
+  StripeMap m;
+  rs_verify_map(rs, c, m);
+  for (int nu = 1; nu <= max_errors; ++nu) {
+    // the Hankel system sum_k sigma_k S'_(j+k) = S'_(j+nu), j = 0..nu-1, by elimination
+    uint8_t M[kWideMaxT][kWideMaxT + 1];
+    for (int j = 0; j < nu; ++j)
+      for (int k = 0; k <= nu; ++k) M[j][k] = s[j + k];
+    bool singular = false;
+    for (int col = 0; col < nu && !singular; ++col) {
+      int piv = -1;
+      for (int r = col; r < nu && piv < 0; ++r)
+        if (M[r][col]) piv = r;
+      if (piv < 0) {
+        singular = true;
+        break;
+      }
+      for (int k = 0; k <= nu; ++k) std::swap(M[col][k], M[piv][k]);
+      const uint8_t inv = F.inv(M[col][col]);
+      for (int k = 0; k <= nu; ++k) M[col][k] = F.mul(M[col][k], inv);
+      for (int r = 0; r < nu; ++r) {
+        const uint8_t f = M[r][col];
+        if (r == col || !f) continue;
+        for (int k = 0; k <= nu; ++k) M[r][k] ^= F.mul(f, M[col][k]);
+      }
+    }
+    if (singular) continue;
+    uint8_t sigma[kWideMaxT + 1];
+    for (int k = 0; k < nu; ++k) sigma[k] = M[k][nu];
+    sigma[nu] = 1;
+    // every remaining power sum
+    bool ok = true;
+    for (int j = nu; j + nu < e && ok; ++j) {
+      uint8_t v = 0;
+      for (int k = 0; k <= nu; ++k) v ^= F.mul(sigma[k], s[j + k]);
+      ok = v == 0;
+    }
+    if (!ok) continue;
+    // exactly nu of this stripe's points are roots of z^nu ^ sigma_(nu-1) z^(nu-1) ^ ... ^ sigma_0
+    int col[kWideMaxT], nroots = 0;
+    for (int i = 0; i < n; ++i) {
+      uint8_t v = 0;
+      for (int k = nu; k >= 0; --k) v = F.mul(v, alpha[i]) ^ sigma[k];
+      if (v != 0) continue;
+      if (nroots < nu) col[nroots] = i;
+      ++nroots;
+    }
+    if (nroots != nu) continue;
+    // the Vandermonde system sum_i y_i X_i^k = S'_k, k < nu: with b(z) = locator / (z ^ X_i),
+    // y_i = sum_k b_k S'_k / b(X_i)
+    uint8_t x[kWideMaxT];
+    for (int i = 0; i < nu && ok; ++i) {
+      const uint8_t X = alpha[col[i]];
+      uint8_t b = 1, num = 0, den = 0;
+      for (int k = nu - 1; k >= 0; --k) {
+        num ^= F.mul(b, s[k]);
+        den = F.mul(den, X) ^ b;
+        b = F.mul(b, X) ^ sigma[k];
+      }
+      x[i] = den ? F.mul(F.mul(num, F.inv(den)), F.inv(u[col[i]])) : 0;
+      ok = x[i] != 0;
+    }
+    if (!ok) continue;
+    // the correction's own syndrome
+    for (int j = 0; j < e && ok; ++j) {
+      uint8_t got = 0;
+      for (int i = 0; i < nu; ++i)
+        got ^= col[i] < d ? F.mul(m.coef[static_cast<size_t>(j) * d + col[i]], x[i])
+                          : static_cast<uint8_t>(j == col[i] - d ? x[i] : 0);
+      ok = got == S[j];
+    }
+    if (!ok) continue;
+    for (int i = 0; i < nu; ++i) cols_out[i] = col[i], values_out[i] = x[i];
+    *count_out = nu;
+    return 0;
+  }
+  return 0;
+}
+
+int repair_wide_job(const redset_hip_rs* rs, int c, const std::vector<uint8_t*>& data,
+                    const std::vector<uint8_t*>& parity, int row, RepairWideJobDesc& out) {
+  const Field& F = field();
+  std::vector<uint8_t> u;
+  if (int rc = rs_power_basis_wide(rs, c, out.alpha, u, out.winv)) return rc;
+  StripeMap m;
+  rs_verify_map(rs, c, m);
+  if (data.size() != m.in.size() || parity.size() != m.out.size())
+    return fail("repair_wide: stripe %d takes %zu data and %zu parity cells", c, m.in.size(), m.out.size());
+  out.cells = RepairJobDesc();
+  out.cells.data = data;
+  out.cells.parity = parity;
+  out.cells.coef = m.coef;
+  for (const CellRef& r : m.in) out.cells.member.push_back(r.rank);
+  for (const CellRef& r : m.out) out.cells.member.push_back(r.rank);
+  out.cells.row = row;
+  out.invu.resize(u.size());
+  for (size_t i = 0; i < u.size(); ++i) out.invu[i] = F.inv(u[i]);
   return 0;
 }
 

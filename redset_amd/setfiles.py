@@ -336,7 +336,7 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
 
 
 def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: bool = True,
-               checksums: bool = False, max_errors: int = 1) -> Dict:
+               checksums: bool = False, max_errors: Optional[int] = 1, wide: bool = False) -> Dict:
     """Scrub one RS set on disk (2 <= e <= 4) and correct, in place, every
     byte column with one wrong byte (redset_amd.stream.rs_repair_stream):
     only the wrong bytes' cell slices are rewritten, and members each damaged
@@ -370,7 +370,12 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
     ``max_errors=2`` (e = 4 only, else ValueError): columns with two wrong
     bytes are corrected too and counted in ``pair_columns``; a column with
     three may then be miscorrected, as two are at e = 2, and ``checksums``
-    stays the arbiter."""
+    stays the arbiter.
+    ``wide=True``: the set has 5 <= e <= 8 parity rows (else ValueError) and
+    goes through stream.rs_repair_wide_stream: columns with up to
+    ``max_errors`` wrong bytes (1 .. e // 2; None: e // 2) are corrected,
+    ``multi_columns`` counts those with 2, 3 and 4, and ``checksums`` is the
+    arbiter of a column with more."""
     f, reds, files, lost = _read_set(redundancy_files)
     p, k = f.ranks, f.encoding
     if lost:
@@ -379,11 +384,14 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
         raise ValueError(f"{f.scheme} set with {k} parity row(s): one row locates nothing; the tool here is a "
                          "rebuild (rebuild_set) of the member that the checksum sidecar names "
                          "(verify_set(checksums=True))")
-    if k > 4:
-        raise ValueError(f"RS set with {k} parity rows: repair is built for 2..4; rebuild_set the located member")
-    from .codec import check_max_errors
+    from .codec import check_max_errors, wide_max_errors
 
-    check_max_errors(max_errors, k)
+    if wide:
+        max_errors = wide_max_errors(max_errors, k)
+    else:
+        if k > 4:
+            raise ValueError(f"RS set with {k} parity rows: repair is built for 2..4; rebuild_set the located member")
+        check_max_errors(max_errors, k)
     stored = _read_sidecar(reds, p, f.chunk) if checksums else None
     hsize = [f.header_size[r] for r in range(p)]
     codec = _codec("RS", p, k)
@@ -391,8 +399,8 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
     def run(writable, do_apply):
         io = stream.FileIO(files, reds, hsize, f.chunk, writable=writable)
         try:
-            return stream.rs_repair_stream(codec, f.chunk, io, slice_bytes=slice_bytes, apply=do_apply,
-                                           max_errors=max_errors)
+            fn = stream.rs_repair_wide_stream if wide else stream.rs_repair_stream
+            return fn(codec, f.chunk, io, slice_bytes=slice_bytes, apply=do_apply, max_errors=max_errors)
         finally:
             io.close()
 
@@ -406,7 +414,9 @@ def repair_set(redundancy_files: Sequence[str], slice_bytes: int = 0, apply: boo
     for key in ("verify_mismatch_bytes", "corrected_bytes", "unlocated_columns", "remaining_mismatch_bytes",
                 "damaged_stripes", "repair_units", "cells_written"):
         out[key] = int(res[key])
-    if max_errors == 2:
+    if wide:
+        out["multi_columns"] = list(res["multi_columns"])
+    elif max_errors == 2:
         out["pair_columns"] = int(res["pair_columns"])
     for c in range(p):
         if not res["corrected"][c].any() and not res["unlocated"][c]:

@@ -158,6 +158,31 @@ def rs_repair_stream(codec, chunk: int, io, first: int = 0, nstripes: int = 0, s
     return out
 
 
+def rs_repair_wide_stream(codec, chunk: int, io, first: int = 0, nstripes: int = 0, slice_bytes: int = 0,
+                          io_threads: int = 0, apply: bool = True, max_errors: Optional[int] = None) -> dict:
+    """rs_repair_stream for sets with 5 <= e <= 8 (include/redset_hip.h
+    redset_hip_rs_repair_wide_stream): every byte column with up to
+    ``max_errors`` wrong bytes (1 .. e // 2; None: e // 2) is corrected. The
+    same fields, plus ``multi_columns`` [3]: the columns corrected with 2, 3
+    and 4 wrong bytes."""
+    from .codec import repair_arrays, wide_max_errors
+
+    max_errors = wide_max_errors(max_errors, codec.encoding)
+    n, p = (nstripes if nstripes > 0 else codec.ranks), codec.ranks
+    st, summ = _lib.StreamStats(), _lib.RepairSummary()
+    cells = (_lib.RepairCell * max(1, n * p))()
+    stripes = (_lib.RepairStripe * max(1, n))()
+    multi = (ctypes.c_ulonglong * 3)()
+    _lib.check(_lib.load().redset_hip_rs_repair_wide_stream(
+        codec._h, chunk, first, nstripes, slice_bytes, io_threads, ctypes.byref(io.io), int(bool(apply)), max_errors,
+        ctypes.byref(st), cells, n * p, stripes, n, ctypes.byref(summ), multi), "rs_repair_wide_stream")
+    corrected, first_off, unloc, first_unloc = repair_arrays(cells, stripes, n, p)
+    out = summ.as_dict()
+    out.update({"multi_columns": [int(x) for x in multi], "corrected": corrected, "first": first_off,
+                "unlocated": unloc, "first_unlocated": first_unloc, "stats": st.as_dict()})
+    return out
+
+
 def rs_rebuild_checked_stream(codec, lost: Sequence[int], chunk: int, io, first: int = 0, nstripes: int = 0,
                               slice_bytes: int = 0, io_threads: int = 0, fix_survivors: bool = False) -> dict:
     """Rebuild the lost members of a host-resident RS set (0 < lost < e <= 4)
