@@ -54,7 +54,8 @@ enum {
   REDSET_HIP_PLAN_RS_REPAIR = 8,
   REDSET_HIP_PLAN_RS_REBUILD_CHECKED = 9,
   REDSET_HIP_PLAN_RS_REPAIR2 = 10,
-  REDSET_HIP_PLAN_RS_REPAIR_WIDE = 11
+  REDSET_HIP_PLAN_RS_REPAIR_WIDE = 11,
+  REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE = 12
 };
 
 typedef struct {
@@ -408,6 +409,74 @@ int redset_hip_plan_rebuild_checked_report(const redset_hip_plan* plan, void* st
 typedef struct { unsigned long long corrected_bytes, unlocated_columns;
                  int stripes_with_findings, cells_written; } redset_hip_rebuild_checked_summary;
 
+/* ---- checked rebuild, wide (5 <= e <= 8, several wrong bytes a column) -- */
+/*
+ * The checked rebuild for RS sets with 5 <= e <= 8 parity rows and 0 < k < e
+ * lost members: s = e - k spare rows, t = s / 2. The survivors' code has
+ * distance s + 1; per byte column up to max_errors <= t wrong survivor bytes
+ * are located and taken out of the rebuilt bytes (and corrected in place with
+ * fix_survivors). s odd: t + 1 wrong bytes are always detected (unlocated).
+ * s even: t + 1 wrong bytes may MIScorrect (the member checksums arbitrate).
+ * s == 1: damage is detected, never located. An unlocated column stores the
+ * plain rebuild's bytes, bit for bit.
+ *
+ * The arithmetic, per stripe, from "repair_wide"'s power basis (points
+ * alpha_i, multipliers u_i, winv * H[:, i] = u_i * (1, alpha_i, ..)): with
+ * the lost cells read as zero, S' = winv * S holds the power sums of errors
+ * and erasures together. Gamma(z) = prod over the lost cells of (z ^ alpha_l)
+ * = sum_m Gamma_m z^m is the erasure locator, in the roots (the point 0
+ * counts). The modified sums T_j = sum_{m=0..k} Gamma_m S'_(j+m), j = 0 ..
+ * s-1, vanish on the lost cells and are plain power sums on the survivors:
+ * T_j = sum_i (u'_i x_i) alpha_i^j over the wrong survivor cells, u'_i = u_i *
+ * Gamma(alpha_i). All of it is one s x (d + e) matrix C = F * winv * H, F the
+ * banded matrix of Gamma's coefficients: survivor column i of C is
+ * u'_i * (1, alpha_i, .., alpha_i^(s-1)), lost columns are zero. The rebuild
+ * rows B stay redset_hip_rs_decode_matrix's coefficients (identity on the
+ * lost columns), which makes an unchecked column the plain rebuild's.
+ */
+
+/* check_basis_wide (host): alpha and uprime (d + e entries each, columns as
+ * redset_hip_rs_check_matrix; uprime is 0 on the lost columns), mat_out =
+ * [C ; B], e x (d + e) bytes row-major (s check rows first), cols_lost_out
+ * (may be NULL): the column of rebuild_ranks[i]. Before returning, C's closed
+ * form is checked on all d + e columns and every rebuild row on the lost
+ * columns and against the row space of H. Errors: e outside 5..8, missing
+ * outside 1..e-1, p + e > 256, unsorted, duplicate or out-of-range ranks. */
+int redset_hip_rs_check_basis_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                                   unsigned char* alpha, unsigned char* uprime, unsigned char* mat_out,
+                                   int* cols_lost_out);
+/* The verdict on one byte column (host; the rule the kernel applies
+ * literally): `reduced` is the s bytes T. For nu = 1 .. max_errors, in this
+ * order, the first nu is answered for which all of this holds: the nu x nu
+ * Hankel system sum_k sigma_k T_(j+k) = T_(j+nu), j < nu, has a unique
+ * solution; it satisfies the same equation for every remaining j (j + nu <
+ * s); the locator has exactly nu distinct roots among the points of the
+ * stripe's surviving cells; the values x_i = y_i / u'_i are all nonzero; and
+ * the correction's own image under C equals T. *count_out = nu, members_out
+ * ascending with values_out beside them (room for 3 each); anything else
+ * gives *count_out = 0. max_errors in 1 .. s/2; with s == 1 only 0 is legal
+ * and the answer is always 0. */
+int redset_hip_rs_locate_reduced_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                                      const unsigned char* reduced, int max_errors, int* members_out,
+                                      unsigned char* values_out, int* count_out);
+/* The plan (gf_rebuild_checked_wide_kernel<s>): contract and footprint as
+ * redset_hip_rs_plan_rebuild_checked -- two launches, no allocation, no host
+ * synchronisation, capture-safe, no block waits on another. Plan info: kind
+ * 12, jobs = p, bytes as kind 9. Refused at plan time: e outside 5..8,
+ * missing == 0, missing >= e, max_errors out of range, bad ranks, and a shape
+ * whose tables do not fit a CU's LDS. */
+int redset_hip_rs_plan_rebuild_checked_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks,
+                                            unsigned char* const* lofi, unsigned char* const* parity, size_t chunk_size,
+                                            size_t cell_stride, int fix_survivors, int max_errors,
+                                            redset_hip_plan** out);
+/* As redset_hip_plan_rebuild_checked_report -- every byte of a correction is
+ * counted -- plus multi_columns[stripe * 2 + nu - 2] (2 * p entries, may be
+ * NULL): the columns corrected with nu = 2, 3 wrong survivor bytes. */
+int redset_hip_plan_rebuild_checked_wide_report(const redset_hip_plan* plan, void* stream,
+                                                redset_hip_repair_cell* cells, int ncells,
+                                                redset_hip_repair_stripe* stripes, int nstripes,
+                                                unsigned long long* multi_columns);
+
 /* ---- member checksums (zlib CRC-32 on the device) --------------------- */
 /*
  * The parity says whether a stripe is consistent, not which bytes are wrong
@@ -605,6 +674,17 @@ int redset_hip_rs_rebuild_checked_stream(const redset_hip_rs* rs, int missing, c
                                          redset_hip_stream_stats* stats, redset_hip_repair_cell* cells, int ncells,
                                          redset_hip_repair_stripe* stripes, int nstripes_out,
                                          redset_hip_rebuild_checked_summary* summary);
+/* The same loop with the wide kernel (5 <= e <= 8, max_errors as the plan's,
+ * see "checked rebuild, wide" above); multi_columns_out (2 entries, may be
+ * NULL) = the columns corrected with 2 and 3 wrong survivor bytes. */
+int redset_hip_rs_rebuild_checked_wide_stream(const redset_hip_rs* rs, int missing, const int* rebuild_ranks,
+                                              size_t chunk_size, int first_stripe, int nstripes, size_t slice_bytes,
+                                              int io_threads, const redset_hip_io* io, int fix_survivors,
+                                              int max_errors, redset_hip_stream_stats* stats,
+                                              redset_hip_repair_cell* cells, int ncells,
+                                              redset_hip_repair_stripe* stripes, int nstripes_out,
+                                              redset_hip_rebuild_checked_summary* summary,
+                                              unsigned long long* multi_columns_out);
 
 /* CRC-32 of byte spans of a host-resident set, in the members' own
  * coordinates: the same read -> H2D -> kernel pipeline with the CRC kernels,

@@ -13,6 +13,7 @@ from .codec import (  # noqa: F401
     Plan,
     RSCodec,
     RebuildCheckedPlan,
+    RebuildCheckedWidePlan,
     Repair2Plan,
     RepairPlan,
     RepairWidePlan,
@@ -30,6 +31,6 @@ from .codec import (  # noqa: F401
 )
 from .checksum import Crc32Plan, crc32_combine  # noqa: F401
 from .setfiles import rebuild_set, repair_set, verify_set  # noqa: F401
-from .stream import rs_rebuild_checked_stream, rs_repair_stream, rs_repair_wide_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
+from .stream import rs_rebuild_checked_stream, rs_rebuild_checked_wide_stream, rs_repair_stream, rs_repair_wide_stream, rs_verify_stream, xor_verify_stream  # noqa: F401
 
 __version__ = "0.1.0"

@@ -28,6 +28,7 @@ PLAN_XOR_VERIFY = 6
 PLAN_CRC32 = 7
 PLAN_RS_REPAIR = 8
 PLAN_RS_REBUILD_CHECKED = 9
+PLAN_RS_REBUILD_CHECKED_WIDE = 12
 
 # every symbol include/redset_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -110,6 +111,11 @@ EXPORTED_SYMBOLS = (
     "redset_hip_rs_plan_repair_wide",
     "redset_hip_plan_repair_wide_report",
     "redset_hip_rs_repair_wide_stream",
+    "redset_hip_rs_check_basis_wide",
+    "redset_hip_rs_locate_reduced_wide",
+    "redset_hip_rs_plan_rebuild_checked_wide",
+    "redset_hip_plan_rebuild_checked_wide_report",
+    "redset_hip_rs_rebuild_checked_wide_stream",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -449,6 +455,20 @@ _SIGNATURES = {
     "redset_hip_rs_repair_wide_stream": (
         c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_int, _IOP, c_int, c_int, _STP, POINTER(RepairCell),
                 c_int, POINTER(RepairStripe), c_int, POINTER(RepairSummary), POINTER(c_ulonglong)]),
+    "redset_hip_rs_check_basis_wide": (
+        c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_ubyte), POINTER(c_ubyte), POINTER(c_ubyte),
+                POINTER(c_int)]),
+    "redset_hip_rs_locate_reduced_wide": (
+        c_int, [c_void_p, c_int, POINTER(c_int), c_int, POINTER(c_ubyte), c_int, POINTER(c_int), POINTER(c_ubyte),
+                POINTER(c_int)]),
+    "redset_hip_rs_plan_rebuild_checked_wide": (
+        c_int, [c_void_p, c_int, POINTER(c_int), _PP, _PP, c_size_t, c_size_t, c_int, c_int, POINTER(c_void_p)]),
+    "redset_hip_plan_rebuild_checked_wide_report": (
+        c_int, [c_void_p, c_void_p, POINTER(RepairCell), c_int, POINTER(RepairStripe), c_int, POINTER(c_ulonglong)]),
+    "redset_hip_rs_rebuild_checked_wide_stream": (
+        c_int, [c_void_p, c_int, POINTER(c_int), c_size_t, c_int, c_int, c_size_t, c_int, _IOP, c_int, c_int, _STP,
+                POINTER(RepairCell), c_int, POINTER(RepairStripe), c_int, POINTER(RebuildCheckedSummary),
+                POINTER(c_ulonglong)]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

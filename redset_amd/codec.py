@@ -151,6 +151,22 @@ def wide_max_errors(max_errors: Optional[int], encoding: int) -> int:
     return int(max_errors)
 
 
+def checked_wide_max_errors(max_errors: Optional[int], encoding: int, lost: int) -> int:
+    """The correction levels of the wide checked rebuild (5 <= e <= 8, s =
+    e - lost spare rows): 1 .. s // 2 (0 where s == 1), None meaning s // 2."""
+    if not 5 <= encoding <= 8:
+        raise ValueError(f"wide checked rebuild on a set with {encoding} parity rows: it is built for 5..8")
+    if not 0 < lost < encoding:
+        raise ValueError(f"wide checked rebuild of {lost} lost members: {encoding} parity rows take 1..{encoding - 1}")
+    t = (encoding - lost) // 2
+    if max_errors is None:
+        return t
+    if not min(1, t) <= max_errors <= t:
+        raise ValueError(f"max_errors={max_errors}: {encoding - lost} spare rows locate {min(1, t)}..{t} wrong bytes "
+                         "per column")
+    return int(max_errors)
+
+
 def repair_arrays(cells, stripes, n: int, p: int):
     """(corrected[n, p], first[n, p], unlocated[n], first_unlocated[n]) of
     redset_hip_repair_cell / redset_hip_repair_stripe arrays."""
@@ -237,6 +253,26 @@ class RebuildCheckedPlan(Plan):
         _lib.check(_lib.load().redset_hip_plan_rebuild_checked_report(self._h, _stream_handle(stream), cells, p * p,
                                                                       stripes, p), "plan_rebuild_checked_report")
         return repair_arrays(cells, stripes, p, p)
+
+
+class RebuildCheckedWidePlan(Plan):
+    """A wide checked rebuild plan (RS sets with 5 <= e <= 8): per byte
+    column up to ``max_errors`` <= (e - k) // 2 wrong survivor bytes are
+    located and taken out of the rebuilt bytes (include/redset_hip.h,
+    "checked rebuild, wide")."""
+
+    def report(self, stream=None):
+        """RebuildCheckedPlan.report's four arrays -- every byte of a
+        correction is counted -- and ``multi_columns`` [p, 2]: the columns of
+        each stripe corrected with 2 and 3 wrong survivor bytes. Waits for the
+        work on ``stream``."""
+        p = int(self.info.ranks)
+        cells = (_lib.RepairCell * (p * p))()
+        stripes = (_lib.RepairStripe * p)()
+        multi = (ctypes.c_ulonglong * (2 * p))()
+        _lib.check(_lib.load().redset_hip_plan_rebuild_checked_wide_report(
+            self._h, _stream_handle(stream), cells, p * p, stripes, p, multi), "plan_rebuild_checked_wide_report")
+        return repair_arrays(cells, stripes, p, p) + (np.array(multi[:2 * p], dtype=np.uint64).reshape(p, 2),)
 
 
 class RSCodec:
@@ -374,6 +410,58 @@ class RSCodec:
             "rs_plan_rebuild_checked",
         )
         return RebuildCheckedPlan(h, (self, lofi, parity))
+
+    def plan_rebuild_checked_wide(self, rebuild_ranks: Sequence[int], lofi, parity, chunk_size: int,
+                                  cell_stride: Optional[int] = None, fix_survivors: bool = False,
+                                  max_errors: Optional[int] = None) -> "RebuildCheckedWidePlan":
+        """plan_rebuild_checked for sets with 5 <= e <= 8 and 0 <
+        len(rebuild_ranks) < e: per byte column up to ``max_errors`` wrong
+        survivor bytes (1 .. (e - k) // 2; None: (e - k) // 2) are located,
+        taken out of the rebuilt bytes and, with ``fix_survivors``, corrected
+        in place. Other e, or max_errors out of range: ValueError."""
+        ranks = sorted(rebuild_ranks)
+        max_errors = checked_wide_max_errors(max_errors, self.encoding, len(ranks))
+        stride = chunk_size if cell_stride is None else cell_stride
+        r = (c_int * max(1, len(ranks)))(*ranks)
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_rebuild_checked_wide(self._h, len(ranks), r, a, b, chunk_size, stride,
+                                                                int(bool(fix_survivors)), max_errors,
+                                                                ctypes.byref(h)),
+            "rs_plan_rebuild_checked_wide",
+        )
+        return RebuildCheckedWidePlan(h, (self, lofi, parity))
+
+    def check_basis_wide(self, rebuild_ranks: Sequence[int], chunk_id: int):
+        """``(alpha, uprime, M, lost_cols)`` of stripe chunk_id with these
+        members lost (ranks as given: the library refuses unsorted ones): M
+        is [e, d + e] -- e - k check rows u'_i * alpha_i^j, zero on the lost
+        columns, then the k rebuild rows (include/redset_hip.h
+        redset_hip_rs_check_basis_wide)."""
+        k, e, n = len(rebuild_ranks), self.encoding, self.ranks
+        r = (c_int * max(1, k))(*[int(x) for x in rebuild_ranks])
+        alpha, up, buf, cols = (c_ubyte * n)(), (c_ubyte * n)(), (c_ubyte * (e * n))(), (c_int * max(1, k))()
+        _lib.check(_lib.load().redset_hip_rs_check_basis_wide(self._h, k, r, chunk_id, alpha, up, buf, cols),
+                   "rs_check_basis_wide")
+        as_np = lambda b: np.frombuffer(bytes(b), dtype=np.uint8).copy()  # noqa: E731
+        return as_np(alpha), as_np(up), as_np(buf).reshape(e, n), [int(cols[i]) for i in range(k)]
+
+    def locate_reduced_wide(self, rebuild_ranks: Sequence[int], chunk_id: int, reduced,
+                            max_errors: Optional[int] = None):
+        """``[(member, value), ...]``: the up to ``max_errors`` (None:
+        (e - k) // 2) surviving members, ascending, whose wrong bytes give
+        these e - k modified sums, with the error values; empty when clean or
+        unlocated (include/redset_hip.h redset_hip_rs_locate_reduced_wide)."""
+        ranks = sorted(rebuild_ranks)
+        r = (c_int * max(1, len(ranks)))(*ranks)
+        t = (self.encoding - len(ranks)) // 2
+        syn = (c_ubyte * 8)(*[int(x) for x in reduced])
+        mem, val, n = (c_int * 3)(), (c_ubyte * 3)(), c_int(0)
+        _lib.check(_lib.load().redset_hip_rs_locate_reduced_wide(
+            self._h, len(ranks), r, chunk_id, syn, t if max_errors is None else int(max_errors), mem, val,
+            ctypes.byref(n)), "rs_locate_reduced_wide")
+        return [(int(mem[i]), int(val[i])) for i in range(n.value)]
 
     def check_matrix(self, rebuild_ranks: Sequence[int], chunk_id: int):
         """``(M, lost_cols)`` of stripe chunk_id with these members lost: M is

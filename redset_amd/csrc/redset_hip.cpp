@@ -23,6 +23,7 @@
 #include "crc32.h"
 #include "gf256.h"
 #include "rebuild_checked.h"
+#include "rebuild_checked_wide.h"
 #include "repair.h"
 #include "repair2.h"
 #include "repair_wide.h"
@@ -85,6 +86,9 @@ struct redset_hip_plan {
   redset_hip::CheckedLaunch checked{};
   void* d_checked = nullptr;
   unsigned long long* d_checked_report = nullptr;
+  // wide checked rebuild plans (REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE): their
+  // launch, over the same two allocations (the nu histogram at the report's end)
+  redset_hip::CheckedWideLaunch checked_wide{};
 };
 
 namespace {
@@ -1637,6 +1641,146 @@ int redset_hip_plan_rebuild_checked_report(const redset_hip_plan* plan, void* st
   return REDSET_SUCCESS;
 }
 
+int redset_hip_rs_check_basis_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                                   unsigned char* alpha, unsigned char* uprime, unsigned char* mat_out,
+                                   int* cols_lost_out) {
+  if (!rs || !alpha || !uprime || !mat_out) return fail("check_basis_wide: null argument");
+  redset_hip::CheckBasisWide B;
+  if (int rc = redset_hip::rs_check_basis_wide(rs, missing, rebuild_ranks, chunk_id, B)) return rc;
+  std::memcpy(alpha, B.alpha.data(), B.alpha.size());
+  std::memcpy(uprime, B.uprime.data(), B.uprime.size());
+  std::memcpy(mat_out, B.X.M.data(), B.X.M.size());
+  for (int i = 0; cols_lost_out && i < missing; ++i) cols_lost_out[i] = B.X.lost_cols[static_cast<size_t>(i)];
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_locate_reduced_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int chunk_id,
+                                      const unsigned char* reduced, int max_errors, int* members_out,
+                                      unsigned char* values_out, int* count_out) {
+  if (!rs || !reduced || !members_out || !values_out || !count_out) return fail("locate_reduced_wide: null argument");
+  *count_out = 0;
+  redset_hip::CheckBasisWide B;
+  if (int rc = redset_hip::rs_check_basis_wide(rs, missing, rebuild_ranks, chunk_id, B)) return rc;
+  int cols[redset_hip::kCwMaxT], n = 0;
+  uint8_t x[redset_hip::kCwMaxT];
+  if (int rc = redset_hip::locate_reduced_wide(B, reduced, max_errors, cols, x, &n)) return rc;
+  std::vector<std::pair<int, uint8_t>> found;
+  for (int i = 0; i < n; ++i) found.emplace_back(B.X.cells[static_cast<size_t>(cols[i])].rank, x[i]);
+  std::sort(found.begin(), found.end());
+  for (int i = 0; i < n; ++i) members_out[i] = found[static_cast<size_t>(i)].first, values_out[i] = found[static_cast<size_t>(i)].second;
+  *count_out = n;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_rs_plan_rebuild_checked_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks,
+                                            unsigned char* const* lofi, unsigned char* const* parity, size_t chunk_size,
+                                            size_t stride, int fix_survivors, int max_errors, redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  const int p = rs->ranks, e = rs->encoding, k = missing, ns = p - k, s = e - k;
+  if (e < redset_hip::kWideMinE || e > redset_hip::kWideMaxE)
+    return fail("plan_rebuild_checked_wide: encoding %d: the wide checked rebuild is built for %d..%d parity rows", e,
+                redset_hip::kWideMinE, redset_hip::kWideMaxE);
+  if (k == 0)
+    return fail("plan_rebuild_checked_wide: no member is lost (use the repair plan, redset_hip_rs_plan_repair_wide)");
+  if (k < 0 || k > e) return fail("plan_rebuild_checked_wide: cannot rebuild %d members with %d parity chunks", k, e);
+  if (k == e)
+    return fail("plan_rebuild_checked_wide: %d lost members of %d parity rows: nothing left to check (use the rebuild "
+                "plan, redset_hip_rs_plan_rebuild)", k, e);
+  if (max_errors < std::min(1, s / 2) || max_errors > s / 2)
+    return fail("plan_rebuild_checked_wide: max_errors %d: %d spare rows locate %d..%d wrong bytes per column",
+                max_errors, s, std::min(1, s / 2), s / 2);
+  if (redset_hip::checked_wide_lds_bytes(ns) > redset_hip::kWideLdsLimit)
+    return fail("plan_rebuild_checked_wide: RS(%d,%d) with %d lost takes %zu bytes of LDS a block, a CU has %zu", p, e, k,
+                redset_hip::checked_wide_lds_bytes(ns), redset_hip::kWideLdsLimit);
+  std::vector<redset_hip::CheckedWideJobDesc> jobs(static_cast<size_t>(p));
+  const SetLayout L{lofi, parity, stride};
+  for (int c = 0; c < p; ++c) {
+    redset_hip::CheckBasisWide B;
+    if (int rc = redset_hip::rs_check_basis_wide(rs, k, rebuild_ranks, c, B)) return rc;
+    std::vector<uint8_t*> in, lostp;
+    for (int i = 0; i < p; ++i)
+      if (std::find(B.X.lost_cols.begin(), B.X.lost_cols.end(), i) == B.X.lost_cols.end())
+        in.push_back(L.at(B.X.cells[static_cast<size_t>(i)]));
+    for (int i : B.X.lost_cols) lostp.push_back(L.at(B.X.cells[static_cast<size_t>(i)]));
+    redset_hip::checked_wide_job(B, in, lostp, c, jobs[static_cast<size_t>(c)]);
+  }
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE;
+  plan->info.ranks = p;
+  plan->info.encoding = e;
+  plan->info.missing = k;
+  plan->info.chunk_size = chunk_size;
+  plan->info.jobs = p;
+  plan->info.launches = chunk_size > 0 ? 2 : 1;
+  plan->info.bytes_read = static_cast<unsigned long long>(p) * ns * chunk_size;
+  plan->info.bytes_written = static_cast<unsigned long long>(p) * k * chunk_size;
+  redset_hip::CheckedWideLaunch& R = plan->checked_wide;
+  R.njobs = p;
+  R.ns = ns;
+  R.e = e;
+  R.k = k;
+  R.p = p;
+  R.fix_survivors = fix_survivors ? 1 : 0;
+  R.max_errors = max_errors;
+  R.nbytes = chunk_size;
+  R.base = 0;
+  R.ncells = p * p;
+  R.nstripes = p;
+  const size_t nh = redset_hip::kCwMaxT - 1;
+  const size_t words = 2 * static_cast<size_t>(R.ncells) + (2 + nh) * static_cast<size_t>(R.nstripes);
+  void* rp = nullptr;
+  int rc = hip_check(hipMalloc(&rp, words * sizeof(unsigned long long)), "hipMalloc(wide checked rebuild report)");
+  plan->d_checked_report = static_cast<unsigned long long*>(rp);
+  R.cell_report = plan->d_checked_report;
+  R.stripe_report = plan->d_checked_report + 2 * static_cast<size_t>(R.ncells);
+  R.multi_report = R.stripe_report + 2 * static_cast<size_t>(R.nstripes);
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::checked_wide_prepare(ns, s)),
+                           "wide checked rebuild LDS attribute");
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::checked_wide_upload(jobs, ns, e, k, &plan->d_checked, R)),
+                           "wide checked rebuild plan upload");
+  // a report read before the first execute says "nothing found"
+  rc = rc ? rc : hip_check(static_cast<hipError_t>(redset_hip::launch_checked_wide_reset(R, nullptr)),
+                           "wide checked rebuild report reset");
+  rc = rc ? rc : hip_check(hipStreamSynchronize(nullptr), "wide checked rebuild report reset");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  R.blocks_per_job = redset_hip::checked_blocks_per_job(p, chunk_size);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+int redset_hip_plan_rebuild_checked_wide_report(const redset_hip_plan* plan, void* stream,
+                                                redset_hip_repair_cell* cells, int ncells,
+                                                redset_hip_repair_stripe* stripes, int nstripes,
+                                                unsigned long long* multi_columns) {
+  if (!plan) return fail("rebuild_checked_wide_report: null plan");
+  if (plan->info.kind != REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE)
+    return fail("rebuild_checked_wide_report: not a wide checked rebuild plan (kind %d)", plan->info.kind);
+  const redset_hip::CheckedWideLaunch& R = plan->checked_wide;
+  if (cells && ncells < R.ncells)
+    return fail("rebuild_checked_wide_report: room for %d cells, the plan reports %d", ncells, R.ncells);
+  if ((stripes || multi_columns) && nstripes < R.nstripes)
+    return fail("rebuild_checked_wide_report: room for %d stripes, the plan reports %d", nstripes, R.nstripes);
+  const size_t nc = static_cast<size_t>(R.ncells), ns = static_cast<size_t>(R.nstripes), nh = redset_hip::kCwMaxT - 1;
+  std::vector<unsigned long long> raw(2 * nc + (2 + nh) * ns);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = hip_check(hipMemcpyAsync(raw.data(), plan->d_checked_report, raw.size() * sizeof(unsigned long long),
+                                        hipMemcpyDeviceToHost, s),
+                         "wide checked rebuild report copy"))
+    return rc;
+  if (int rc = hip_check(hipStreamSynchronize(s), "wide checked rebuild report sync")) return rc;
+  for (size_t i = 0; cells && i < nc; ++i) cells[i] = redset_hip_repair_cell{raw[i], raw[nc + i]};
+  for (size_t i = 0; stripes && i < ns; ++i) stripes[i] = redset_hip_repair_stripe{raw[2 * nc + i], raw[2 * nc + ns + i]};
+  for (size_t i = 0; multi_columns && i < nh * ns; ++i) multi_columns[i] = raw[2 * nc + 2 * ns + i];
+  return REDSET_SUCCESS;
+}
+
 int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   if (!plan) return fail("null plan");
   for (const auto& C : plan->gf_checks)
@@ -1673,6 +1817,12 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
       return hip_check(static_cast<hipError_t>(e), "checked rebuild report reset");
     return hip_check(static_cast<hipError_t>(redset_hip::launch_checked(plan->checked, stream)),
                      "gf_rebuild_checked launch");
+  }
+  if (plan->info.kind == REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE) {
+    if (int e = redset_hip::launch_checked_wide_reset(plan->checked_wide, stream))
+      return hip_check(static_cast<hipError_t>(e), "wide checked rebuild report reset");
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_checked_wide(plan->checked_wide, stream)),
+                     "gf_rebuild_checked_wide launch");
   }
   for (const GfLaunch& G : plan->gf_launches)
     if (int e = redset_hip::launch_gf(G, stream)) return hip_check(static_cast<hipError_t>(e), "gf_mac launch");

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "gf256.h"
+#include "rebuild_checked_wide.h"
 #include "repair2.h"
 #include "repair_wide.h"
 
@@ -496,6 +497,189 @@ int repair_wide_job(const redset_hip_rs* rs, int c, const std::vector<uint8_t*>&
   out.invu.resize(u.size());
   for (size_t i = 0; i < u.size(); ++i) out.invu[i] = F.inv(u[i]);
   return 0;
+}
+
+int rs_check_basis_wide(const redset_hip_rs* rs, int missing, const int* rebuild_ranks, int c, CheckBasisWide& out) {
+  const int p = rs->ranks, e = rs->encoding, d = p - e, n = p, k = missing, s = e - k;
+  const Field& F = field();
+  if (e < kWideMinE || e > kWideMaxE)
+    return fail("check_basis_wide: encoding %d: the wide checked rebuild is built for %d..%d parity rows", e, kWideMinE,
+                kWideMaxE);
+  if (k < 1 || k >= e)
+    return fail("check_basis_wide: %d lost members of %d parity rows: the wide checked rebuild takes 1..%d", k, e, e - 1);
+  if (!rebuild_ranks) return fail("check_basis_wide: null rebuild_ranks");
+  for (int i = 0; i < k; ++i) {
+    if (rebuild_ranks[i] < 0 || rebuild_ranks[i] >= p)
+      return fail("check_basis_wide: rebuild rank %d out of range", rebuild_ranks[i]);
+    if (i > 0 && rebuild_ranks[i] == rebuild_ranks[i - 1])
+      return fail("check_basis_wide: rebuild rank %d listed twice", rebuild_ranks[i]);
+    if (i > 0 && rebuild_ranks[i] < rebuild_ranks[i - 1]) return fail("check_basis_wide: rebuild_ranks must be ascending");
+  }
+  std::vector<uint8_t> u, winv;
+  if (int rc = rs_power_basis_wide(rs, c, out.alpha, u, winv)) return rc;  // chunk id, p + e > 256
+  // B, the cells and the lost columns are rs_check_matrix's: the decode's own rows
+  if (int rc = rs_check_matrix(rs, k, rebuild_ranks, c, out.X)) return rc;
+  CheckMatrix& X = out.X;
+  StripeMap vm;
+  rs_verify_map(rs, c, vm);
+  auto h = [&](int j, int i) {  // H = [A | I]
+    return i < d ? vm.coef[static_cast<size_t>(j) * d + i] : static_cast<uint8_t>(j == i - d);
+  };
+  // Gamma(z) = prod over the lost columns of (z ^ alpha_l), coefficients g[0..k], g[k] = 1
+  uint8_t g[kWideMaxE + 1] = {1};
+  for (int i = 0; i < k; ++i) {
+    const uint8_t a = out.alpha[static_cast<size_t>(X.lost_cols[static_cast<size_t>(i)])];
+    g[i + 1] = 0;
+    for (int m = i + 1; m > 0; --m) g[m] = static_cast<uint8_t>(g[m - 1] ^ F.mul(g[m], a));
+    g[0] = F.mul(g[0], a);
+  }
+  // C = F * (W^-1 * H), F[j][j + m] = g[m]
+  std::vector<uint8_t> P(static_cast<size_t>(e) * n, 0);
+  for (int t = 0; t < e; ++t)
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < e; ++j) P[static_cast<size_t>(t) * n + i] ^= F.mul(winv[static_cast<size_t>(t) * e + j], h(j, i));
+  for (int j = 0; j < s; ++j)
+    for (int i = 0; i < n; ++i) {
+      uint8_t v = 0;
+      for (int m = 0; m <= k; ++m) v ^= F.mul(g[m], P[static_cast<size_t>(j + m) * n + i]);
+      X.M[static_cast<size_t>(j) * n + i] = v;
+    }
+  // the structure is checked, not assumed: column i of C is u_i Gamma(alpha_i) (1, alpha_i, ..), zero where lost
+  out.uprime.assign(static_cast<size_t>(n), 0);
+  for (int i = 0; i < n; ++i) {
+    const uint8_t a = out.alpha[static_cast<size_t>(i)];
+    uint8_t ga = 0;
+    for (int m = k; m >= 0; --m) ga = static_cast<uint8_t>(F.mul(ga, a) ^ g[m]);
+    const bool lost = std::find(X.lost_cols.begin(), X.lost_cols.end(), i) != X.lost_cols.end();
+    if (lost != (ga == 0))
+      return fail("check_basis_wide: stripe %d: the erasure locator and the lost columns disagree at column %d", c, i);
+    uint8_t v = F.mul(u[static_cast<size_t>(i)], ga);
+    out.uprime[static_cast<size_t>(i)] = v;
+    for (int j = 0; j < s; ++j, v = F.mul(v, a))
+      if (X.M[static_cast<size_t>(j) * n + i] != v)
+        return fail("check_basis_wide: stripe %d column %d is not u' * alpha^%d in check row %d (RS(%d,%d), %d lost)", c,
+                    i, j, j, p, e, k);
+  }
+  // every rebuild row, with its one on its lost column, is y * H for y = its parity columns
+  for (int r = 0; r < k; ++r) {
+    const uint8_t* b = X.M.data() + static_cast<size_t>(s + r) * n;
+    for (int l = 0; l < k; ++l)
+      if (b[X.lost_cols[static_cast<size_t>(l)]] != (l == r ? 1 : 0))
+        return fail("check_basis_wide: stripe %d rebuild row %d is not the identity on the lost columns", c, r);
+    for (int i = 0; i < d; ++i) {
+      uint8_t v = 0;
+      for (int j = 0; j < e; ++j) v ^= F.mul(b[d + j], h(j, i));
+      if (v != b[i]) return fail("check_basis_wide: stripe %d rebuild row %d is not a combination of the parity rows", c, r);
+    }
+  }
+  return 0;
+}
+
+int locate_reduced_wide(const CheckBasisWide& Bs, const uint8_t* T, int max_errors, int* cols_out, uint8_t* values_out,
+                        int* count_out) {
+  const Field& F = field();
+  const CheckMatrix& X = Bs.X;
+  const int n = X.d + X.e, s = X.e - X.k, t = s / 2;
+  *count_out = 0;
+  if (max_errors < std::min(1, t) || max_errors > t)
+    return fail("locate_reduced_wide: max_errors %d: %d spare rows locate %d..%d wrong bytes per column", max_errors, s,
+                std::min(1, t), t);
+  bool any = false;
+  for (int j = 0; j < s; ++j) any = any || T[j] != 0;
+  if (!any) return 0;
+  for (int nu = 1; nu <= max_errors; ++nu) {
+    // the Hankel system sum_k sigma_k T_(j+k) = T_(j+nu), j = 0..nu-1, by elimination
+    uint8_t M[kCwMaxT][kCwMaxT + 1];
+    for (int j = 0; j < nu; ++j)
+      for (int k = 0; k <= nu; ++k) M[j][k] = T[j + k];
+    bool singular = false;
+    for (int col = 0; col < nu && !singular; ++col) {
+      int piv = -1;
+      for (int r = col; r < nu && piv < 0; ++r)
+        if (M[r][col]) piv = r;
+      if (piv < 0) {
+        singular = true;
+        break;
+      }
+      for (int k = 0; k <= nu; ++k) std::swap(M[col][k], M[piv][k]);
+      const uint8_t inv = F.inv(M[col][col]);
+      for (int k = 0; k <= nu; ++k) M[col][k] = F.mul(M[col][k], inv);
+      for (int r = 0; r < nu; ++r) {
+        const uint8_t f = M[r][col];
+        if (r == col || !f) continue;
+        for (int k = 0; k <= nu; ++k) M[r][k] ^= F.mul(f, M[col][k]);
+      }
+    }
+    if (singular) continue;
+    uint8_t sigma[kCwMaxT + 1];
+    for (int k = 0; k < nu; ++k) sigma[k] = M[k][nu];
+    sigma[nu] = 1;
+    // every remaining equation
+    bool ok = true;
+    for (int j = nu; j + nu < s && ok; ++j) {
+      uint8_t v = 0;
+      for (int k = 0; k <= nu; ++k) v ^= F.mul(sigma[k], T[j + k]);
+      ok = v == 0;
+    }
+    if (!ok) continue;
+    // exactly nu of the surviving cells' points are roots
+    int col[kCwMaxT], nroots = 0;
+    for (int i = 0; i < n; ++i) {
+      if (Bs.uprime[static_cast<size_t>(i)] == 0) continue;  // a lost column
+      uint8_t v = 0;
+      for (int k = nu; k >= 0; --k) v = F.mul(v, Bs.alpha[static_cast<size_t>(i)]) ^ sigma[k];
+      if (v != 0) continue;
+      if (nroots < nu) col[nroots] = i;
+      ++nroots;
+    }
+    if (nroots != nu) continue;
+    // with b(z) = locator / (z ^ X_i): y_i = sum_k b_k T_k / b(X_i), x_i = y_i / u'_i
+    uint8_t x[kCwMaxT];
+    for (int i = 0; i < nu && ok; ++i) {
+      const uint8_t Xi = Bs.alpha[static_cast<size_t>(col[i])];
+      uint8_t b = 1, num = 0, den = 0;
+      for (int k = nu - 1; k >= 0; --k) {
+        num ^= F.mul(b, T[k]);
+        den = F.mul(den, Xi) ^ b;
+        b = F.mul(b, Xi) ^ sigma[k];
+      }
+      x[i] = den ? F.mul(F.mul(num, F.inv(den)), F.inv(Bs.uprime[static_cast<size_t>(col[i])])) : 0;
+      ok = x[i] != 0;
+    }
+    if (!ok) continue;
+    // the correction's own image under the check rows
+    for (int j = 0; j < s && ok; ++j) {
+      uint8_t got = 0;
+      for (int i = 0; i < nu; ++i) got ^= F.mul(X.M[static_cast<size_t>(j) * n + col[i]], x[i]);
+      ok = got == T[j];
+    }
+    if (!ok) continue;
+    for (int i = 0; i < nu; ++i) cols_out[i] = col[i], values_out[i] = x[i];
+    *count_out = nu;
+    return 0;
+  }
+  return 0;
+}
+
+void checked_wide_job(const CheckBasisWide& Bs, const std::vector<uint8_t*>& in, const std::vector<uint8_t*>& out,
+                      int row, CheckedWideJobDesc& J) {
+  const Field& F = field();
+  const CheckMatrix& X = Bs.X;
+  const int n = X.d + X.e;
+  J = CheckedWideJobDesc();
+  J.cells.in = in;
+  J.cells.out = out;
+  J.cells.row = row;
+  std::vector<int> cols;
+  for (int i = 0; i < n; ++i)
+    if (std::find(X.lost_cols.begin(), X.lost_cols.end(), i) == X.lost_cols.end()) cols.push_back(i);
+  for (int i : cols) {
+    J.cells.member.push_back(X.cells[static_cast<size_t>(i)].rank);
+    J.alpha.push_back(Bs.alpha[static_cast<size_t>(i)]);
+    J.invu.push_back(F.inv(Bs.uprime[static_cast<size_t>(i)]));
+  }
+  for (int j = 0; j < X.e; ++j)
+    for (int i : cols) J.cells.coef.push_back(X.M[static_cast<size_t>(j) * n + i]);
 }
 
 namespace {

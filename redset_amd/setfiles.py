@@ -226,7 +226,8 @@ def _read_set(redundancy_files: Sequence[str]):
 
 
 def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums: bool = False,
-                check_survivors: bool = False, fix_survivors: bool = False) -> Dict:
+                check_survivors: bool = False, fix_survivors: bool = False, wide: bool = False,
+                max_errors: Optional[int] = None) -> Dict:
     """Rebuild the lost members of one set from the redundancy files that can
     still be read (``redundancy_files`` may name lost ones too). A member is
     lost when its redundancy file is unreadable or shorter than header + k
@@ -254,7 +255,13 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
     e > 4 are a ValueError, never a silent plain rebuild. Survivors' data
     files are opened read-only; with ``fix_survivors`` (which needs
     check_survivors) a second pass opens for writing only the members the
-    first located corrections in, and writes the corrected bytes back."""
+    first located corrections in, and writes the corrected bytes back.
+    ``wide=True`` (with check_survivors): the set has 5 <= e <= 8 parity rows
+    (else ValueError) and goes through stream.rs_rebuild_checked_wide_stream:
+    per byte column up to ``max_errors`` wrong survivor bytes (1 ..
+    (e - lost) // 2; None: that many) are located, ``multi_columns`` counts
+    the columns with 2 and 3, and ``checksums`` is the arbiter of a column
+    with more."""
     f, reds, files, lost = _read_set(redundancy_files)
     p, k = f.ranks, f.encoding
     out = {"scheme": f.scheme, "ranks": p, "encoding": k, "chunk": f.chunk, "missing": lost,
@@ -269,11 +276,17 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
         if f.scheme != "RS":
             raise ValueError(f"check_survivors: an {f.scheme} set has one parity row and the rebuild needs it; "
                              "nothing is left to check the survivors with")
-        if k > 4:
+        if not wide and k > 4:
             raise ValueError(f"check_survivors: RS set with {k} parity rows: the checked rebuild is built for 2..4")
+        if wide and not 5 <= k <= 8:
+            raise ValueError(f"check_survivors: RS set with {k} parity rows: the wide checked rebuild is built for 5..8")
         if len(lost) == k:
             raise ValueError(f"check_survivors: {len(lost)} members lost of {k} parity rows: the rebuild needs every "
                              "row, nothing is left to check the survivors with")
+    if check_survivors and wide:
+        from .codec import checked_wide_max_errors
+
+        max_errors = checked_wide_max_errors(max_errors, k, len(lost))
     stored = _read_sidecar(reds, p, f.chunk) if checksums else None
     hsize = [f.header_size.get(r, 0) for r in range(p)]
     for r in lost:
@@ -293,6 +306,9 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
         def run(writable, fix):
             cio = stream.FileIO(files, reds, hsize, f.chunk, writable=writable)
             try:
+                if wide:
+                    return stream.rs_rebuild_checked_wide_stream(codec, lost, f.chunk, cio, slice_bytes=slice_bytes,
+                                                                 fix_survivors=fix, max_errors=max_errors)
                 return stream.rs_rebuild_checked_stream(codec, lost, f.chunk, cio, slice_bytes=slice_bytes,
                                                         fix_survivors=fix)
             finally:
@@ -311,6 +327,8 @@ def rebuild_set(redundancy_files: Sequence[str], slice_bytes: int = 0, checksums
         out["unlocated_columns"] = int(res["unlocated_columns"])
         out["unlocated_stripes"] = [c for c in range(p) if res["unlocated"][c]]
         out["trusted"] = out["unlocated_columns"] == 0
+        if wide:
+            out["multi_columns"] = list(res["multi_columns"])
     else:
         io = stream.FileIO(files, reds, hsize, f.chunk, writable=[r in lost for r in range(p)])
         try:

@@ -213,6 +213,35 @@ def rs_rebuild_checked_stream(codec, lost: Sequence[int], chunk: int, io, first:
     return out
 
 
+def rs_rebuild_checked_wide_stream(codec, lost: Sequence[int], chunk: int, io, first: int = 0, nstripes: int = 0,
+                                   slice_bytes: int = 0, io_threads: int = 0, fix_survivors: bool = False,
+                                   max_errors: Optional[int] = None) -> dict:
+    """rs_rebuild_checked_stream for sets with 5 <= e <= 8 (include/redset_hip.h
+    redset_hip_rs_rebuild_checked_wide_stream): per byte column up to
+    ``max_errors`` wrong survivor bytes (1 .. (e - k) // 2; None: (e - k) // 2)
+    are located and kept out of the rebuilt bytes. The same fields, plus
+    ``multi_columns`` [2]: the columns corrected with 2 and 3 wrong bytes."""
+    from .codec import checked_wide_max_errors, repair_arrays
+
+    r = sorted(lost)
+    max_errors = checked_wide_max_errors(max_errors, codec.encoding, len(r))
+    arr = (c_int * max(1, len(r)))(*r)
+    n, p = (nstripes if nstripes > 0 else codec.ranks), codec.ranks
+    st, summ = _lib.StreamStats(), _lib.RebuildCheckedSummary()
+    cells = (_lib.RepairCell * max(1, n * p))()
+    stripes = (_lib.RepairStripe * max(1, n))()
+    multi = (ctypes.c_ulonglong * 2)()
+    _lib.check(_lib.load().redset_hip_rs_rebuild_checked_wide_stream(
+        codec._h, len(r), arr, chunk, first, nstripes, slice_bytes, io_threads, ctypes.byref(io.io),
+        int(bool(fix_survivors)), max_errors, ctypes.byref(st), cells, n * p, stripes, n, ctypes.byref(summ), multi),
+        "rs_rebuild_checked_wide_stream")
+    corrected, first_off, unloc, first_unloc = repair_arrays(cells, stripes, n, p)
+    out = summ.as_dict()
+    out.update({"multi_columns": [int(x) for x in multi], "corrected": corrected, "first": first_off,
+                "unlocated": unloc, "first_unlocated": first_unloc, "stats": st.as_dict()})
+    return out
+
+
 def crc32_stream(chunk: int, io, spans: Sequence[Tuple[int, int, int, int]], slice_bytes: int = 0,
                  io_threads: int = 0) -> dict:
     """zlib CRC-32 of every span ``(rank, kind, offset, length)`` of a
