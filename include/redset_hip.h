@@ -55,7 +55,9 @@ enum {
   REDSET_HIP_PLAN_RS_REBUILD_CHECKED = 9,
   REDSET_HIP_PLAN_RS_REPAIR2 = 10,
   REDSET_HIP_PLAN_RS_REPAIR_WIDE = 11,
-  REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE = 12
+  REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE = 12,
+  REDSET_HIP_PLAN_RS_ENCODE_CRC32 = 13,
+  REDSET_HIP_PLAN_XOR_ENCODE_CRC32 = 14
 };
 
 typedef struct {
@@ -510,6 +512,37 @@ int redset_hip_plan_crc32(const redset_hip_crc_range* ranges, int nranges, redse
 /* The CRCs of the last execute (ncrcs at least the plan's ranges); ordered on
  * `stream` after the work already there, waits for it. */
 int redset_hip_plan_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs);
+
+/* ---- encode and checksum in one read ---------------------------------- */
+/*
+ * The encode of redset_hip_rs_plan_encode / redset_hip_xor_plan_encode (same
+ * set layout, same stripe map, the same parity bytes) that also leaves the
+ * CRC-32 of every cell of the set, data and parity: one kernel reads every
+ * data cell once, forms and stores the parity, and runs all d + e cells of the
+ * stripe through the CRC from the registers it holds -- a parity cell's
+ * checksum is taken from the values that were stored and a data cell's from
+ * the bytes that were encoded, not from a later read of memory. A second small
+ * launch (the CRC plan's finish kernel) folds the per-tile remainders; only
+ * the < 512 bytes after a cell's last whole 512-B segment are read again.
+ * Executes through redset_hip_plan_execute: launches only, capture-safe (a
+ * chain of two kernel nodes), no allocation, no host synchronisation, and no
+ * block waits on another, so neither the ring nor the hang count can move.
+ * Only bytes [0, chunk_size) of a parity cell are written. Plan info: kind 13
+ * (RS) or 14 (XOR), jobs = p, bytes_read = p * d * chunk_size, bytes_written =
+ * p * e * chunk_size. One plan must not execute on two streams at once.
+ * Refused at plan time (REDSET_FAILURE, redset_hip_last_error says why):
+ * stripes wider than one kernel pass (RS: p - e > 16 or e > 4; XOR: p - 1 >
+ * 16), a member pointer or cell_stride that is not 16-B aligned, chunk_size 0.
+ */
+int redset_hip_rs_plan_encode_crc32(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                                    size_t chunk_size, size_t cell_stride, redset_hip_plan** out);
+int redset_hip_xor_plan_encode_crc32(int ranks, unsigned char* const* lofi, unsigned char* const* xorc,
+                                     size_t chunk_size, size_t cell_stride, redset_hip_plan** out);
+/* The p * p CRCs of the last execute (ncrcs at least that): crcs[r * p + c] is
+ * member r's cell c -- its data cells in logical-file order, then its parity
+ * slots -- zlib's CRC-32 of that cell's chunk_size bytes. Ordered on `stream`
+ * after the work already there, waits for it. */
+int redset_hip_plan_encode_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs);
 
 /* ---- stripe primitives (one stripe, device pointers) ----------------- */
 

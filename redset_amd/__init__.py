@@ -10,6 +10,7 @@ header-driven rebuild over files (:mod:`redset_amd.setfiles`).
 """
 from ._lib import LIB_PATH, RedsetHipError, RedsetHipUnavailable, load  # noqa: F401
 from .codec import (  # noqa: F401
+    EncodeCrcPlan,
     Plan,
     RSCodec,
     RebuildCheckedPlan,
@@ -25,6 +26,7 @@ from .codec import (  # noqa: F401
     hang_faults,
     xor_combine,
     xor_plan_encode,
+    xor_plan_encode_crc32,
     xor_plan_rebuild,
     xor_plan_repair,
     xor_plan_verify,

@@ -29,6 +29,8 @@ PLAN_CRC32 = 7
 PLAN_RS_REPAIR = 8
 PLAN_RS_REBUILD_CHECKED = 9
 PLAN_RS_REBUILD_CHECKED_WIDE = 12
+PLAN_RS_ENCODE_CRC32 = 13
+PLAN_XOR_ENCODE_CRC32 = 14
 
 # every symbol include/redset_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -116,6 +118,9 @@ EXPORTED_SYMBOLS = (
     "redset_hip_rs_plan_rebuild_checked_wide",
     "redset_hip_plan_rebuild_checked_wide_report",
     "redset_hip_rs_rebuild_checked_wide_stream",
+    "redset_hip_rs_plan_encode_crc32",
+    "redset_hip_xor_plan_encode_crc32",
+    "redset_hip_plan_encode_crc32_report",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -469,6 +474,9 @@ _SIGNATURES = {
         c_int, [c_void_p, c_int, POINTER(c_int), c_size_t, c_int, c_int, c_size_t, c_int, _IOP, c_int, c_int, _STP,
                 POINTER(RepairCell), c_int, POINTER(RepairStripe), c_int, POINTER(RebuildCheckedSummary),
                 POINTER(c_ulonglong)]),
+    "redset_hip_rs_plan_encode_crc32": (c_int, [c_void_p, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
+    "redset_hip_xor_plan_encode_crc32": (c_int, [c_int, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
+    "redset_hip_plan_encode_crc32_report": (c_int, [c_void_p, c_void_p, POINTER(c_uint), c_int]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

@@ -275,6 +275,23 @@ class RebuildCheckedWidePlan(Plan):
         return repair_arrays(cells, stripes, p, p) + (np.array(multi[:2 * p], dtype=np.uint64).reshape(p, 2),)
 
 
+class EncodeCrcPlan(Plan):
+    """An encode plan that checksums what it encodes: execute() reads every
+    data cell once, stores the parity cells of the plain encode plan and
+    leaves the zlib CRC-32 of every cell of the set (include/redset_hip.h,
+    "encode and checksum in one read")."""
+
+    def report(self, stream=None) -> np.ndarray:
+        """The CRCs of the last execute: a ``(p, p)`` uint32 array indexed
+        ``[member, cell]`` -- the member's data cells in logical-file order,
+        then its parity slots. Waits for the work on ``stream``."""
+        p = int(self.info.ranks)
+        crcs = (ctypes.c_uint * (p * p))()
+        _lib.check(_lib.load().redset_hip_plan_encode_crc32_report(self._h, _stream_handle(stream), crcs, p * p),
+                   "plan_encode_crc32_report")
+        return np.array(crcs[:], dtype=np.uint32).reshape(p, p)
+
+
 class RSCodec:
     """GF(2^8) tables + encoding matrix for a set of ``ranks`` members with
     ``encoding`` parity cells per stripe (redset_construct_rs,
@@ -322,6 +339,20 @@ class RSCodec:
             "rs_plan_encode",
         )
         return Plan(h, (self, lofi, parity))
+
+    def plan_encode_crc32(self, lofi, parity, chunk_size: int,
+                          cell_stride: Optional[int] = None) -> "EncodeCrcPlan":
+        """plan_encode that also checksums every cell in the same read:
+        p - e <= 16 data cells and e <= 4 parity cells a stripe, pointers and
+        stride 16-B aligned (anything else is refused, never run another way)."""
+        stride = chunk_size if cell_stride is None else cell_stride
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_encode_crc32(self._h, a, b, chunk_size, stride, ctypes.byref(h)),
+            "rs_plan_encode_crc32",
+        )
+        return EncodeCrcPlan(h, (self, lofi, parity))
 
     def plan_rebuild(self, rebuild_ranks: Sequence[int], lofi, parity, chunk_size: int,
                      cell_stride: Optional[int] = None) -> Plan:
@@ -569,6 +600,20 @@ def xor_plan_encode(ranks: int, lofi, xorc, chunk_size: int, cell_stride: Option
         "xor_plan_encode",
     )
     return Plan(h, (lofi, xorc))
+
+
+def xor_plan_encode_crc32(ranks: int, lofi, xorc, chunk_size: int,
+                          cell_stride: Optional[int] = None) -> EncodeCrcPlan:
+    """xor_plan_encode that also checksums every cell in the same read
+    (ranks - 1 <= 16; pointers and stride 16-B aligned)."""
+    stride = chunk_size if cell_stride is None else cell_stride
+    a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in xorc])
+    h = c_void_p()
+    _lib.check(
+        _lib.load().redset_hip_xor_plan_encode_crc32(ranks, a, b, chunk_size, stride, ctypes.byref(h)),
+        "xor_plan_encode_crc32",
+    )
+    return EncodeCrcPlan(h, (lofi, xorc))
 
 
 def xor_plan_rebuild(ranks: int, root: int, lofi, xorc, chunk_size: int,

@@ -55,5 +55,8 @@ CrcRange crc_range(const void* ptr, unsigned long long len);
 const unsigned* crc_device_tables();
 // both kernels of one execute on `stream`; returns hipError_t as int
 int launch_crc32(const CrcLaunch& L, void* stream);
+// crc32_finish_kernel alone, over tile remainders another kernel left in
+// L.rem (encode_crc_kernels.hip); L.tile0 / L.ntiles are not read
+int launch_crc32_finish(const CrcLaunch& L, void* stream);
 
 }  // namespace redset_hip

@@ -25,43 +25,13 @@
 
 #include "codec_kernels.h"
 #include "crc32.h"
+#include "crc32_device.h"
 
 namespace redset_hip {
 
 namespace {
 
-constexpr unsigned kPoly = 0xEDB88320u;
-constexpr int kSliceTables = 16;
-constexpr int kFoldLevels = 8;  // 2^8 = kCrcLanes segments
-constexpr int kSliceWords = kSliceTables * 256;
-constexpr int kTableWords = kSliceWords + kFoldLevels * 4 * 256;
 static_assert(kCrcLanes == 256 && kCrcSeg % 64 == 0, "the fold is written for 4 waves of 64 lanes");
-
-__device__ __forceinline__ unsigned mulmod_dev(unsigned a, unsigned b) {
-  unsigned p = 0;
-  for (int i = 0; i < 32; ++i) {
-    p ^= (a & 0x80000000u) ? b : 0u;
-    a <<= 1;
-    b = (b >> 1) ^ ((b & 1u) ? kPoly : 0u);
-  }
-  return p;
-}
-
-// 16 more bytes through the register
-__device__ __forceinline__ unsigned step16(const unsigned* sl, unsigned crc, uint4 w) {
-  const unsigned a = w.x ^ crc, b = w.y, c = w.z, d = w.w;
-  return sl[15 * 256 + (a & 255u)] ^ sl[14 * 256 + ((a >> 8) & 255u)] ^ sl[13 * 256 + ((a >> 16) & 255u)] ^
-         sl[12 * 256 + (a >> 24)] ^ sl[11 * 256 + (b & 255u)] ^ sl[10 * 256 + ((b >> 8) & 255u)] ^
-         sl[9 * 256 + ((b >> 16) & 255u)] ^ sl[8 * 256 + (b >> 24)] ^ sl[7 * 256 + (c & 255u)] ^
-         sl[6 * 256 + ((c >> 8) & 255u)] ^ sl[5 * 256 + ((c >> 16) & 255u)] ^ sl[4 * 256 + (c >> 24)] ^
-         sl[3 * 256 + (d & 255u)] ^ sl[2 * 256 + ((d >> 8) & 255u)] ^ sl[1 * 256 + ((d >> 16) & 255u)] ^
-         sl[0 * 256 + (d >> 24)];
-}
-
-// a remainder advanced by one fold level's byte count
-__device__ __forceinline__ unsigned advance(const unsigned* t, unsigned r) {
-  return t[r & 255u] ^ t[256 + ((r >> 8) & 255u)] ^ t[512 + ((r >> 16) & 255u)] ^ t[768 + (r >> 24)];
-}
 
 // the 16 bytes at `a` (16-B aligned) with those before `first` read as zero
 __device__ uint4 load16_from(const uint8_t* a, uintptr_t first) {
@@ -248,7 +218,12 @@ int launch_crc32(const CrcLaunch& L, void* stream) {
     hipLaunchKernelGGL(crc32_tiles_kernel, dim3(grid), dim3(kCrcLanes), 0, s, L);
     if (hipError_t e = hipGetLastError()) return e;
   }
-  hipLaunchKernelGGL(crc32_finish_kernel, dim3(L.nranges), dim3(64), 0, s, L);
+  return launch_crc32_finish(L, stream);
+}
+
+int launch_crc32_finish(const CrcLaunch& L, void* stream) {
+  if (L.nranges <= 0) return hipSuccess;
+  hipLaunchKernelGGL(crc32_finish_kernel, dim3(L.nranges), dim3(64), 0, static_cast<hipStream_t>(stream), L);
   return hipGetLastError();
 }
 

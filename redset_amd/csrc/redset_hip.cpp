@@ -21,6 +21,7 @@
 
 #include "codec_kernels.h"
 #include "crc32.h"
+#include "encode_crc.h"
 #include "gf256.h"
 #include "rebuild_checked.h"
 #include "rebuild_checked_wide.h"
@@ -71,6 +72,11 @@ struct redset_hip_plan {
   // tables (ranges, tile numbering, one remainder per tile, the CRCs)
   redset_hip::CrcLaunch crc{};
   void* d_crc = nullptr;
+  // fused encode + CRC plans (REDSET_HIP_PLAN_*_ENCODE_CRC32): the launch over
+  // the plan's one device block (jobs, range numbers, powers of x, and the
+  // finish launch's ranges, tile numbering, remainders and CRCs)
+  redset_hip::EncodeCrcLaunch enc_crc{};
+  void* d_enc_crc = nullptr;
   // repair plans (REDSET_HIP_PLAN_RS_REPAIR): the launch over the plan's
   // device job blob, and both reports in one allocation
   redset_hip::RepairLaunch repair{};
@@ -773,6 +779,115 @@ int finish_verify_plan(int kind, int ranks, int encoding, size_t chunk, const st
   return REDSET_SUCCESS;
 }
 
+// Fused encode + CRC plan from the stripes' encode maps: one job per stripe,
+// one CRC range per cell of the set, numbered as the report orders them
+// (member r's cell c: its data cells, then its parity slots).
+int finish_encode_crc_plan(int kind, int ranks, int encoding, size_t chunk, size_t stride,
+                           const std::vector<StripeMap>& maps, const SetLayout& L, redset_hip_plan** out) {
+  const char* what = kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32 ? "xor_plan_encode_crc32" : "rs_plan_encode_crc32";
+  const int p = ranks, e = encoding, d = p - e;
+  if (chunk == 0) return fail("%s: chunk_size 0", what);
+  if (d > kMaxIn || e > kMaxOut)
+    return fail("%s: %d data and %d parity cells a stripe: one pass takes up to %d and %d", what, d, e, kMaxIn, kMaxOut);
+  if (stride % 16 != 0) return fail("%s: cell_stride %zu is not a multiple of 16", what, stride);
+  for (int r = 0; r < p; ++r)
+    if (!aligned16(L.lofi[r]) || !aligned16(L.parity[r])) return fail("%s: member %d: pointer not 16-B aligned", what, r);
+  const int nc = d + e, ncells = p * p;
+  const unsigned long long tiles = redset_hip::crc_tiles(L.lofi[0], chunk);
+  if (tiles * static_cast<unsigned long long>(ncells) > 0x7fffffffull)
+    return fail("%s: %zu bytes a cell are more than one plan takes", what, chunk);
+  std::vector<GfJob> jobs(static_cast<size_t>(p));
+  std::vector<int> slot(static_cast<size_t>(p) * nc);
+  std::vector<redset_hip::CrcRange> ranges(static_cast<size_t>(ncells));
+  std::vector<int> base(static_cast<size_t>(ncells) + 1);
+  std::vector<char> seen(static_cast<size_t>(ncells), 0);
+  for (int c = 0; c < p; ++c) {
+    const StripeMap& m = maps[static_cast<size_t>(c)];
+    if (static_cast<int>(m.in.size()) != d || static_cast<int>(m.out.size()) != e)
+      return fail("%s: stripe %d has %zu data and %zu parity cells", what, c, m.in.size(), m.out.size());
+    GfJob& J = jobs[static_cast<size_t>(c)];
+    std::memset(&J, 0, sizeof(J));
+    for (int i = 0; i < nc; ++i) {
+      const CellRef& cell = i < d ? m.in[i] : m.out[i - d];
+      uint8_t* ptr = L.at(cell);
+      if (i < d) J.in[i] = ptr;
+      else J.out[i - d] = ptr;
+      const int s = cell.rank * p + (cell.kind == redset_hip::kData ? cell.index : d + cell.index);
+      if (s < 0 || s >= ncells || seen[s]) return fail("%s: stripe %d: cell %d of the map is out of place", what, c, i);
+      seen[s] = 1;
+      slot[static_cast<size_t>(c) * nc + i] = s;
+      ranges[s] = redset_hip::crc_range(ptr, chunk);
+    }
+    for (int j = 0; j < e && !m.xor_only; ++j)
+      for (int i = 0; i < d; ++i) J.coef[j][i] = m.coef[static_cast<size_t>(j) * d + i];
+  }
+  for (int s = 0; s <= ncells; ++s) base[s] = s * static_cast<int>(tiles);
+  unsigned xpow[redset_hip::kCrcLanes];
+  redset_hip::encode_crc_xpow(xpow);
+  auto up16 = [](size_t n) { return (n + 15) & ~size_t(15); };
+  const size_t o_slot = up16(jobs.size() * sizeof(GfJob));
+  const size_t o_xpow = o_slot + up16(slot.size() * sizeof(int));
+  const size_t o_rng = o_xpow + up16(sizeof(xpow));
+  const size_t o_base = o_rng + up16(ranges.size() * sizeof(redset_hip::CrcRange));
+  const size_t o_rem = o_base + up16(base.size() * sizeof(int));
+  const size_t o_crc = o_rem + up16(static_cast<size_t>(tiles) * ncells * sizeof(unsigned));
+  const size_t bytes = o_crc + up16(static_cast<size_t>(ncells) * sizeof(unsigned));
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) return fail("out of host memory");
+  plan->info.kind = kind;
+  plan->info.ranks = p;
+  plan->info.encoding = e;
+  plan->info.chunk_size = chunk;
+  plan->info.jobs = p;
+  plan->info.launches = 2;
+  plan->info.bytes_read = static_cast<unsigned long long>(p) * d * chunk;
+  plan->info.bytes_written = static_cast<unsigned long long>(p) * e * chunk;
+  int rc = hip_check(hipMalloc(&plan->d_enc_crc, bytes), "hipMalloc(encode_crc plan)");
+  char* dev = static_cast<char*>(plan->d_enc_crc);
+  rc = rc ? rc : hip_check(hipMemset(dev, 0, bytes), "hipMemset(encode_crc plan)");
+  auto put = [&](size_t off, const void* src, size_t n) {
+    rc = rc ? rc : hip_check(hipMemcpy(dev + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(encode_crc plan)");
+  };
+  put(0, jobs.data(), jobs.size() * sizeof(GfJob));
+  put(o_slot, slot.data(), slot.size() * sizeof(int));
+  put(o_xpow, xpow, sizeof(xpow));
+  put(o_rng, ranges.data(), ranges.size() * sizeof(redset_hip::CrcRange));
+  put(o_base, base.data(), base.size() * sizeof(int));
+  const unsigned* tables = rc ? nullptr : redset_hip::crc_device_tables();
+  if (!rc && !tables) rc = fail("%s: cannot place the lookup tables on the device", what);
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  redset_hip::EncodeCrcLaunch& E = plan->enc_crc;
+  E.jobs = reinterpret_cast<const GfJob*>(dev);
+  E.slot = reinterpret_cast<const int*>(dev + o_slot);
+  E.xpow = reinterpret_cast<const unsigned*>(dev + o_xpow);
+  E.tables = tables;
+  E.rem = reinterpret_cast<unsigned*>(dev + o_rem);
+  E.njobs = p;
+  E.nin = d;
+  E.nout = e;
+  E.xor_only = kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32 ? 1 : 0;
+  E.tiles = static_cast<int>(tiles);
+  E.nbytes = chunk;
+  E.finish.ranges = reinterpret_cast<const redset_hip::CrcRange*>(dev + o_rng);
+  E.finish.tile_base = reinterpret_cast<const int*>(dev + o_base);
+  E.finish.nranges = ncells;
+  E.finish.tile0 = 0;
+  E.finish.ntiles = static_cast<int>(tiles) * ncells;
+  E.finish.rem = E.rem;
+  E.finish.crcs = reinterpret_cast<unsigned*>(dev + o_crc);
+  E.finish.tables = tables;
+  E.finish.xtile = redset_hip::crc_xpow8(redset_hip::kCrcTile);
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+bool is_encode_crc(const redset_hip_plan* plan) {
+  return plan->info.kind == REDSET_HIP_PLAN_RS_ENCODE_CRC32 || plan->info.kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32;
+}
+
 bool is_verify(const redset_hip_plan* plan) {
   return plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY || plan->info.kind == REDSET_HIP_PLAN_XOR_VERIFY;
 }
@@ -1141,6 +1256,43 @@ int redset_hip_plan_crc32_report(const redset_hip_plan* plan, void* stream, unsi
                          "crc32 report copy"))
     return rc;
   return hip_check(hipStreamSynchronize(s), "crc32 report sync");
+}
+
+int redset_hip_rs_plan_encode_crc32(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                                    size_t chunk_size, size_t stride, redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  std::vector<StripeMap> maps(rs->ranks);
+  for (int c = 0; c < rs->ranks; ++c) redset_hip::rs_encode_map(rs, c, maps[c]);
+  return finish_encode_crc_plan(REDSET_HIP_PLAN_RS_ENCODE_CRC32, rs->ranks, rs->encoding, chunk_size, stride, maps,
+                                SetLayout{lofi, parity, stride}, out);
+}
+
+int redset_hip_xor_plan_encode_crc32(int ranks, unsigned char* const* lofi, unsigned char* const* xorc,
+                                     size_t chunk_size, size_t stride, redset_hip_plan** out) {
+  if (ranks < 2) return fail("XOR needs at least 2 ranks, got %d", ranks);
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(xorc),
+                              ranks, chunk_size, stride, out))
+    return rc;
+  std::vector<StripeMap> maps(ranks);
+  for (int c = 0; c < ranks; ++c) redset_hip::xor_encode_map(ranks, c, maps[c]);
+  return finish_encode_crc_plan(REDSET_HIP_PLAN_XOR_ENCODE_CRC32, ranks, 1, chunk_size, stride, maps,
+                                SetLayout{lofi, xorc, stride}, out);
+}
+
+int redset_hip_plan_encode_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs) {
+  if (!plan || !crcs) return fail("encode_crc32_report: null argument");
+  if (!is_encode_crc(plan)) return fail("encode_crc32_report: not an encode + CRC plan (kind %d)", plan->info.kind);
+  const int n = plan->enc_crc.finish.nranges;
+  if (ncrcs < n) return fail("encode_crc32_report: room for %d CRCs, the plan reports %d", ncrcs, n);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = hip_check(hipMemcpyAsync(crcs, plan->enc_crc.finish.crcs, static_cast<size_t>(n) * sizeof(unsigned),
+                                        hipMemcpyDeviceToHost, s),
+                         "encode_crc32 report copy"))
+    return rc;
+  return hip_check(hipStreamSynchronize(s), "encode_crc32 report sync");
 }
 
 int redset_hip_rs_plan_repair(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
@@ -1796,6 +1948,8 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
   }
   if (plan->info.kind == REDSET_HIP_PLAN_CRC32)
     return hip_check(static_cast<hipError_t>(redset_hip::launch_crc32(plan->crc, stream)), "crc32 launch");
+  if (is_encode_crc(plan))
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_encode_crc(plan->enc_crc, stream)), "encode_crc launch");
   if (plan->info.kind == REDSET_HIP_PLAN_RS_REPAIR) {
     if (int e = redset_hip::launch_repair_reset(plan->repair, stream))
       return hip_check(static_cast<hipError_t>(e), "repair report reset");
@@ -1845,6 +1999,7 @@ void redset_hip_plan_destroy(redset_hip_plan* plan) {
   if (plan->d_report) (void) hipFree(plan->d_report);
   if (plan->d_scratch) (void) hipFree(plan->d_scratch);
   if (plan->d_crc) (void) hipFree(plan->d_crc);
+  if (plan->d_enc_crc) (void) hipFree(plan->d_enc_crc);
   if (plan->d_repair) (void) hipFree(plan->d_repair);
   if (plan->d_repair_report) (void) hipFree(plan->d_repair_report);
   if (plan->d_checked) (void) hipFree(plan->d_checked);
