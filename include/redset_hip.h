@@ -57,7 +57,9 @@ enum {
   REDSET_HIP_PLAN_RS_REPAIR_WIDE = 11,
   REDSET_HIP_PLAN_RS_REBUILD_CHECKED_WIDE = 12,
   REDSET_HIP_PLAN_RS_ENCODE_CRC32 = 13,
-  REDSET_HIP_PLAN_XOR_ENCODE_CRC32 = 14
+  REDSET_HIP_PLAN_XOR_ENCODE_CRC32 = 14,
+  REDSET_HIP_PLAN_RS_VERIFY_CRC32 = 15,
+  REDSET_HIP_PLAN_XOR_VERIFY_CRC32 = 16
 };
 
 typedef struct {
@@ -543,6 +545,39 @@ int redset_hip_xor_plan_encode_crc32(int ranks, unsigned char* const* lofi, unsi
  * slots -- zlib's CRC-32 of that cell's chunk_size bytes. Ordered on `stream`
  * after the work already there, waits for it. */
 int redset_hip_plan_encode_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs);
+
+/* ---- scrub and checksum in one read ----------------------------------- */
+/*
+ * The scrub of redset_hip_rs_plan_verify / redset_hip_xor_plan_verify (same set
+ * layout, same stripe map, the same report rows) that also leaves the CRC-32
+ * of every cell of the set, data and parity: one kernel reads every cell once,
+ * forms the parity of the stored data, compares it with the stored parity and
+ * runs all d + e cells of the stripe through the CRC from the registers it
+ * holds. A parity cell's checksum is of the bytes that were LOADED -- what is
+ * stored, which on a damaged set is not what the data encodes to -- so the
+ * CRCs compare with a sidecar recorded at encode and tell a damaged member
+ * from a damaged parity row where the syndrome cannot (XOR sets, columns with
+ * more wrong bytes than the code places). No cell is written. Executes through
+ * redset_hip_plan_execute: three kernel launches (the report's reset, the
+ * fused kernel, the CRC plan's finish kernel, which reads only the < 512 bytes
+ * after a cell's last whole 512-B segment again), capture-safe, no allocation,
+ * no host synchronisation, and no block waits on another, so neither the ring
+ * nor the hang count can move. Plan info: kind 15 (RS) or 16 (XOR), jobs = p,
+ * bytes_written = 0, bytes_read = p * (d + e) * chunk_size (XOR: p * p *
+ * chunk_size). redset_hip_plan_verify_report and redset_hip_plan_verify_locate
+ * take these plans as they take the verify plans. One plan must not execute on
+ * two streams at once. Refused at plan time (REDSET_FAILURE,
+ * redset_hip_last_error says why): stripes wider than one kernel pass (RS:
+ * p - e > 16 or e > 4; XOR: p - 1 > 16), a member pointer or cell_stride that
+ * is not 16-B aligned, chunk_size 0.
+ */
+int redset_hip_rs_plan_verify_crc32(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                                    size_t chunk_size, size_t cell_stride, redset_hip_plan** out);
+int redset_hip_xor_plan_verify_crc32(int ranks, unsigned char* const* lofi, unsigned char* const* xorc,
+                                     size_t chunk_size, size_t cell_stride, redset_hip_plan** out);
+/* The p * p CRCs of the last execute, indexed and ordered as
+ * redset_hip_plan_encode_crc32_report's: crcs[r * p + c] is member r's cell c. */
+int redset_hip_plan_verify_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs);
 
 /* ---- stripe primitives (one stripe, device pointers) ----------------- */
 

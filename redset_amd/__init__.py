@@ -19,6 +19,7 @@ from .codec import (  # noqa: F401
     RepairPlan,
     RepairWidePlan,
     SetLayout,
+    VerifyCrcPlan,
     VerifyPlan,
     gf_combine,
     cell_stride,
@@ -30,6 +31,7 @@ from .codec import (  # noqa: F401
     xor_plan_rebuild,
     xor_plan_repair,
     xor_plan_verify,
+    xor_plan_verify_crc32,
 )
 from .checksum import Crc32Plan, crc32_combine  # noqa: F401
 from .setfiles import rebuild_set, repair_set, verify_set  # noqa: F401

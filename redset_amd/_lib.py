@@ -121,6 +121,9 @@ EXPORTED_SYMBOLS = (
     "redset_hip_rs_plan_encode_crc32",
     "redset_hip_xor_plan_encode_crc32",
     "redset_hip_plan_encode_crc32_report",
+    "redset_hip_rs_plan_verify_crc32",
+    "redset_hip_xor_plan_verify_crc32",
+    "redset_hip_plan_verify_crc32_report",
 )
 
 # include/redset_hip.h REDSET_HIP_ABI_VERSION: the struct layouts below
@@ -477,6 +480,9 @@ _SIGNATURES = {
     "redset_hip_rs_plan_encode_crc32": (c_int, [c_void_p, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
     "redset_hip_xor_plan_encode_crc32": (c_int, [c_int, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
     "redset_hip_plan_encode_crc32_report": (c_int, [c_void_p, c_void_p, POINTER(c_uint), c_int]),
+    "redset_hip_rs_plan_verify_crc32": (c_int, [c_void_p, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
+    "redset_hip_xor_plan_verify_crc32": (c_int, [c_int, _PP, _PP, c_size_t, c_size_t, POINTER(c_void_p)]),
+    "redset_hip_plan_verify_crc32_report": (c_int, [c_void_p, c_void_p, POINTER(c_uint), c_int]),
     "redset_hip_rccl_available": (c_int, []),
     "redset_hip_rccl_unique_id": (c_int, [POINTER(c_ubyte)]),
     "redset_hip_rccl_transport_create": (c_int, [POINTER(c_ubyte), c_int, c_int, POINTER(Transport), POINTER(c_void_p)]),

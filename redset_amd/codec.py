@@ -129,6 +129,23 @@ class VerifyPlan(Plan):
         return int(m.value), (None if off.value == NO_OFFSET else int(off.value))
 
 
+class VerifyCrcPlan(VerifyPlan):
+    """A verify plan that checksums what it scrubs: execute() reads every
+    cell of the set once, writes none, leaves VerifyPlan's report and the
+    zlib CRC-32 of every cell as stored (include/redset_hip.h, "scrub and
+    checksum in one read")."""
+
+    def crcs(self, stream=None) -> np.ndarray:
+        """The CRCs of the last execute: a ``(p, p)`` uint32 array indexed
+        ``[member, cell]`` -- the member's data cells in logical-file order,
+        then its parity slots. Waits for the work on ``stream``."""
+        p = int(self.info.ranks)
+        crcs = (ctypes.c_uint * (p * p))()
+        _lib.check(_lib.load().redset_hip_plan_verify_crc32_report(self._h, _stream_handle(stream), crcs, p * p),
+                   "plan_verify_crc32_report")
+        return np.array(crcs[:], dtype=np.uint32).reshape(p, p)
+
+
 def check_max_errors(max_errors: int, encoding: int) -> None:
     """The correction levels of repair: 1, or 2 on sets with four parity rows."""
     if max_errors not in (1, 2):
@@ -379,6 +396,20 @@ class RSCodec:
             "rs_plan_verify",
         )
         return VerifyPlan(h, (self, lofi, parity))
+
+    def plan_verify_crc32(self, lofi, parity, chunk_size: int,
+                          cell_stride: Optional[int] = None) -> "VerifyCrcPlan":
+        """plan_verify that also checksums every cell in the same read:
+        p - e <= 16 data cells and e <= 4 parity cells a stripe, pointers and
+        stride 16-B aligned (anything else is refused, never run another way)."""
+        stride = chunk_size if cell_stride is None else cell_stride
+        a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in parity])
+        h = c_void_p()
+        _lib.check(
+            _lib.load().redset_hip_rs_plan_verify_crc32(self._h, a, b, chunk_size, stride, ctypes.byref(h)),
+            "rs_plan_verify_crc32",
+        )
+        return VerifyCrcPlan(h, (self, lofi, parity))
 
     def plan_repair(self, lofi, parity, chunk_size: int, cell_stride: Optional[int] = None,
                     stripes: Optional[Sequence[int]] = None, apply: bool = True, max_errors: int = 1):
@@ -638,6 +669,20 @@ def xor_plan_verify(ranks: int, lofi, xorc, chunk_size: int, cell_stride: Option
         "xor_plan_verify",
     )
     return VerifyPlan(h, (lofi, xorc))
+
+
+def xor_plan_verify_crc32(ranks: int, lofi, xorc, chunk_size: int,
+                          cell_stride: Optional[int] = None) -> VerifyCrcPlan:
+    """xor_plan_verify that also checksums every cell in the same read
+    (ranks - 1 <= 16; pointers and stride 16-B aligned)."""
+    stride = chunk_size if cell_stride is None else cell_stride
+    a, b = _lib.ptr_array([_ptr(x) for x in lofi]), _lib.ptr_array([_ptr(x) for x in xorc])
+    h = c_void_p()
+    _lib.check(
+        _lib.load().redset_hip_xor_plan_verify_crc32(ranks, a, b, chunk_size, stride, ctypes.byref(h)),
+        "xor_plan_verify_crc32",
+    )
+    return VerifyCrcPlan(h, (lofi, xorc))
 
 
 def xor_plan_repair(ranks: int, lofi, xorc, chunk_size: int, cell_stride: Optional[int] = None, stripes=None,

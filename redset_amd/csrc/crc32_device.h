@@ -1,6 +1,6 @@
 // crc32_device.h -- the CRC-32 table layout of crc_device_tables() and the
 // device arithmetic on remainders (crc32.h) shared by the kernels that run a
-// CRC: crc32_kernels.hip and encode_crc_kernels.hip.
+// CRC: crc32_kernels.hip, encode_crc_kernels.hip and verify_crc_kernels.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

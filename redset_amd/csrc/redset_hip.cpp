@@ -29,6 +29,7 @@
 #include "repair2.h"
 #include "repair_wide.h"
 #include "stripe_map.h"
+#include "verify_crc.h"
 
 using redset_hip::CellRef;
 using redset_hip::fail;
@@ -77,6 +78,10 @@ struct redset_hip_plan {
   // finish launch's ranges, tile numbering, remainders and CRCs)
   redset_hip::EncodeCrcLaunch enc_crc{};
   void* d_enc_crc = nullptr;
+  // fused verify + CRC plans (REDSET_HIP_PLAN_*_VERIFY_CRC32): the launch over
+  // the same kind of block (d_enc_crc) and the verify plans' report (d_report,
+  // report_rows; cells and mat for locate)
+  redset_hip::VerifyCrcLaunch ver_crc{};
   // repair plans (REDSET_HIP_PLAN_RS_REPAIR): the launch over the plan's
   // device job blob, and both reports in one allocation
   redset_hip::RepairLaunch repair{};
@@ -779,13 +784,27 @@ int finish_verify_plan(int kind, int ranks, int encoding, size_t chunk, const st
   return REDSET_SUCCESS;
 }
 
-// Fused encode + CRC plan from the stripes' encode maps: one job per stripe,
-// one CRC range per cell of the set, numbered as the report orders them
-// (member r's cell c: its data cells, then its parity slots).
-int finish_encode_crc_plan(int kind, int ranks, int encoding, size_t chunk, size_t stride,
-                           const std::vector<StripeMap>& maps, const SetLayout& L, redset_hip_plan** out) {
-  const char* what = kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32 ? "xor_plan_encode_crc32" : "rs_plan_encode_crc32";
-  const int p = ranks, e = encoding, d = p - e;
+// What the fused codec + CRC launches (encode_crc.h, verify_crc.h) share: the
+// plan's one device block.
+struct FusedCrcBlock {
+  const GfJob* jobs;
+  const int* slot;
+  const unsigned* xpow;
+  const unsigned* tables;
+  unsigned* rem;
+  int tiles;
+  redset_hip::CrcLaunch finish;
+};
+
+// The device block of a fused codec + CRC plan (plan->d_enc_crc) from the
+// stripes' maps (in: the data cells, out: the parity cells): one job per
+// stripe, one CRC range per cell of the set, numbered as the report orders
+// them (member r's cell c: its data cells, then its parity slots). Refuses
+// what the fused kernels do not take.
+int build_fused_crc_block(const char* what, redset_hip_plan* plan, size_t stride, const std::vector<StripeMap>& maps,
+                          const SetLayout& L, FusedCrcBlock* B) {
+  const int p = plan->info.ranks, e = plan->info.encoding, d = p - e;
+  const size_t chunk = plan->info.chunk_size;
   if (chunk == 0) return fail("%s: chunk_size 0", what);
   if (d > kMaxIn || e > kMaxOut)
     return fail("%s: %d data and %d parity cells a stripe: one pass takes up to %d and %d", what, d, e, kMaxIn, kMaxOut);
@@ -832,21 +851,11 @@ int finish_encode_crc_plan(int kind, int ranks, int encoding, size_t chunk, size
   const size_t o_rem = o_base + up16(base.size() * sizeof(int));
   const size_t o_crc = o_rem + up16(static_cast<size_t>(tiles) * ncells * sizeof(unsigned));
   const size_t bytes = o_crc + up16(static_cast<size_t>(ncells) * sizeof(unsigned));
-  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
-  if (!plan) return fail("out of host memory");
-  plan->info.kind = kind;
-  plan->info.ranks = p;
-  plan->info.encoding = e;
-  plan->info.chunk_size = chunk;
-  plan->info.jobs = p;
-  plan->info.launches = 2;
-  plan->info.bytes_read = static_cast<unsigned long long>(p) * d * chunk;
-  plan->info.bytes_written = static_cast<unsigned long long>(p) * e * chunk;
-  int rc = hip_check(hipMalloc(&plan->d_enc_crc, bytes), "hipMalloc(encode_crc plan)");
+  int rc = hip_check(hipMalloc(&plan->d_enc_crc, bytes), "hipMalloc(fused CRC plan)");
   char* dev = static_cast<char*>(plan->d_enc_crc);
-  rc = rc ? rc : hip_check(hipMemset(dev, 0, bytes), "hipMemset(encode_crc plan)");
+  rc = rc ? rc : hip_check(hipMemset(dev, 0, bytes), "hipMemset(fused CRC plan)");
   auto put = [&](size_t off, const void* src, size_t n) {
-    rc = rc ? rc : hip_check(hipMemcpy(dev + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(encode_crc plan)");
+    rc = rc ? rc : hip_check(hipMemcpy(dev + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(fused CRC plan)");
   };
   put(0, jobs.data(), jobs.size() * sizeof(GfJob));
   put(o_slot, slot.data(), slot.size() * sizeof(int));
@@ -855,31 +864,123 @@ int finish_encode_crc_plan(int kind, int ranks, int encoding, size_t chunk, size
   put(o_base, base.data(), base.size() * sizeof(int));
   const unsigned* tables = rc ? nullptr : redset_hip::crc_device_tables();
   if (!rc && !tables) rc = fail("%s: cannot place the lookup tables on the device", what);
-  if (rc) {
+  if (rc) return rc;
+  B->jobs = reinterpret_cast<const GfJob*>(dev);
+  B->slot = reinterpret_cast<const int*>(dev + o_slot);
+  B->xpow = reinterpret_cast<const unsigned*>(dev + o_xpow);
+  B->tables = tables;
+  B->rem = reinterpret_cast<unsigned*>(dev + o_rem);
+  B->tiles = static_cast<int>(tiles);
+  B->finish.ranges = reinterpret_cast<const redset_hip::CrcRange*>(dev + o_rng);
+  B->finish.tile_base = reinterpret_cast<const int*>(dev + o_base);
+  B->finish.nranges = ncells;
+  B->finish.tile0 = 0;
+  B->finish.ntiles = static_cast<int>(tiles) * ncells;
+  B->finish.rem = B->rem;
+  B->finish.crcs = reinterpret_cast<unsigned*>(dev + o_crc);
+  B->finish.tables = tables;
+  B->finish.xtile = redset_hip::crc_xpow8(redset_hip::kCrcTile);
+  return REDSET_SUCCESS;
+}
+
+redset_hip_plan* new_set_plan(int kind, int ranks, int encoding, size_t chunk) {
+  redset_hip_plan* plan = new (std::nothrow) redset_hip_plan;
+  if (!plan) {
+    fail("out of host memory");
+    return nullptr;
+  }
+  plan->info.kind = kind;
+  plan->info.ranks = ranks;
+  plan->info.encoding = encoding;
+  plan->info.chunk_size = chunk;
+  plan->info.jobs = ranks;
+  return plan;
+}
+
+// Fused encode + CRC plan from the stripes' encode maps.
+int finish_encode_crc_plan(int kind, int ranks, int encoding, size_t chunk, size_t stride,
+                           const std::vector<StripeMap>& maps, const SetLayout& L, redset_hip_plan** out) {
+  const char* what = kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32 ? "xor_plan_encode_crc32" : "rs_plan_encode_crc32";
+  const int p = ranks, e = encoding, d = p - e;
+  redset_hip_plan* plan = new_set_plan(kind, p, e, chunk);
+  if (!plan) return REDSET_FAILURE;
+  plan->info.launches = 2;
+  plan->info.bytes_read = static_cast<unsigned long long>(p) * d * chunk;
+  plan->info.bytes_written = static_cast<unsigned long long>(p) * e * chunk;
+  FusedCrcBlock B{};
+  if (int rc = build_fused_crc_block(what, plan, stride, maps, L, &B)) {
     redset_hip_plan_destroy(plan);
     return rc;
   }
   redset_hip::EncodeCrcLaunch& E = plan->enc_crc;
-  E.jobs = reinterpret_cast<const GfJob*>(dev);
-  E.slot = reinterpret_cast<const int*>(dev + o_slot);
-  E.xpow = reinterpret_cast<const unsigned*>(dev + o_xpow);
-  E.tables = tables;
-  E.rem = reinterpret_cast<unsigned*>(dev + o_rem);
+  E.jobs = B.jobs;
+  E.slot = B.slot;
+  E.xpow = B.xpow;
+  E.tables = B.tables;
+  E.rem = B.rem;
   E.njobs = p;
   E.nin = d;
   E.nout = e;
   E.xor_only = kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32 ? 1 : 0;
-  E.tiles = static_cast<int>(tiles);
+  E.tiles = B.tiles;
   E.nbytes = chunk;
-  E.finish.ranges = reinterpret_cast<const redset_hip::CrcRange*>(dev + o_rng);
-  E.finish.tile_base = reinterpret_cast<const int*>(dev + o_base);
-  E.finish.nranges = ncells;
-  E.finish.tile0 = 0;
-  E.finish.ntiles = static_cast<int>(tiles) * ncells;
-  E.finish.rem = E.rem;
-  E.finish.crcs = reinterpret_cast<unsigned*>(dev + o_crc);
-  E.finish.tables = tables;
-  E.finish.xtile = redset_hip::crc_xpow8(redset_hip::kCrcTile);
+  E.finish = B.finish;
+  *out = plan;
+  return REDSET_SUCCESS;
+}
+
+// Fused verify + CRC plan from the stripes' verify maps (the parity cells in
+// parity-row order, so output j reports to the stripe's row j): the block
+// above, the verify plans' report, and what locate needs.
+int finish_verify_crc_plan(int kind, int ranks, int encoding, size_t chunk, size_t stride,
+                           const std::vector<StripeMap>& maps, const SetLayout& L, const redset_hip_rs* rs,
+                           redset_hip_plan** out) {
+  const char* what = kind == REDSET_HIP_PLAN_XOR_VERIFY_CRC32 ? "xor_plan_verify_crc32" : "rs_plan_verify_crc32";
+  const int p = ranks, e = encoding, d = p - e;
+  redset_hip_plan* plan = new_set_plan(kind, p, e, chunk);
+  if (!plan) return REDSET_FAILURE;
+  plan->info.launches = 3;
+  plan->info.bytes_read = static_cast<unsigned long long>(p) * (d + e) * chunk;
+  plan->info.bytes_written = 0;
+  FusedCrcBlock B{};
+  int rc = build_fused_crc_block(what, plan, stride, maps, L, &B);
+  if (!rc) {
+    plan->report_rows = p * e;
+    void* rp = nullptr;
+    rc = hip_check(hipMalloc(&rp, 2 * static_cast<size_t>(plan->report_rows) * sizeof(unsigned long long)),
+                   "hipMalloc(verify report)");
+    plan->d_report = static_cast<unsigned long long*>(rp);
+  }
+  rc = rc ? rc : redset_hip::verify_report_reset(plan->d_report, plan->report_rows, 0, plan->report_rows, nullptr);
+  rc = rc ? rc : hip_check(hipStreamSynchronize(nullptr), "report reset");
+  if (rc) {
+    redset_hip_plan_destroy(plan);
+    return rc;
+  }
+  plan->cells.resize(static_cast<size_t>(p) * p);
+  for (int c = 0; c < p; ++c)
+    for (int s = 0; s < p; ++s) {
+      const CellRef cell = rs ? redset_hip::rs_cell(rs, s, c)
+                              : (s == c ? CellRef{s, redset_hip::kParity, 0}
+                                        : CellRef{s, redset_hip::kData, redset_hip::xor_segment(s, c)});
+      plan->cells[static_cast<size_t>(c) * p + s] = L.at(cell);
+    }
+  if (rs) plan->mat = rs->mat;
+  redset_hip::VerifyCrcLaunch& V = plan->ver_crc;
+  V.jobs = B.jobs;
+  V.slot = B.slot;
+  V.xpow = B.xpow;
+  V.tables = B.tables;
+  V.rem = B.rem;
+  V.report = plan->d_report;
+  V.report_rows = plan->report_rows;
+  V.njobs = p;
+  V.nin = d;
+  V.nout = e;
+  V.xor_only = kind == REDSET_HIP_PLAN_XOR_VERIFY_CRC32 ? 1 : 0;
+  V.tiles = B.tiles;
+  V.nbytes = chunk;
+  V.finish = B.finish;
   *out = plan;
   return REDSET_SUCCESS;
 }
@@ -888,8 +989,19 @@ bool is_encode_crc(const redset_hip_plan* plan) {
   return plan->info.kind == REDSET_HIP_PLAN_RS_ENCODE_CRC32 || plan->info.kind == REDSET_HIP_PLAN_XOR_ENCODE_CRC32;
 }
 
+bool is_verify_crc(const redset_hip_plan* plan) {
+  return plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY_CRC32 || plan->info.kind == REDSET_HIP_PLAN_XOR_VERIFY_CRC32;
+}
+
+// a plan with the verify report: the verify plans and the fused verify + CRC plans
 bool is_verify(const redset_hip_plan* plan) {
-  return plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY || plan->info.kind == REDSET_HIP_PLAN_XOR_VERIFY;
+  return plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY || plan->info.kind == REDSET_HIP_PLAN_XOR_VERIFY ||
+         is_verify_crc(plan);
+}
+
+// RS plans locate; XOR plans answer -1
+bool is_rs_verify(const redset_hip_plan* plan) {
+  return plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY || plan->info.kind == REDSET_HIP_PLAN_RS_VERIFY_CRC32;
 }
 
 // the plan's report as rows, ordered on `stream` after the work there
@@ -1161,7 +1273,7 @@ int redset_hip_plan_verify_locate(const redset_hip_plan* plan, void* stream, int
     if (r.mismatch_bytes) off = std::min(off, r.first_offset);
   }
   *offset_out = off;
-  if (off == ~0ull || plan->info.kind != REDSET_HIP_PLAN_RS_VERIFY) return REDSET_SUCCESS;
+  if (off == ~0ull || !is_rs_verify(plan)) return REDSET_SUCCESS;
   // the stripe's byte column at that offset, member by member
   std::vector<uint8_t> col(static_cast<size_t>(p));
   const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1293,6 +1405,43 @@ int redset_hip_plan_encode_crc32_report(const redset_hip_plan* plan, void* strea
                          "encode_crc32 report copy"))
     return rc;
   return hip_check(hipStreamSynchronize(s), "encode_crc32 report sync");
+}
+
+int redset_hip_rs_plan_verify_crc32(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
+                                    size_t chunk_size, size_t stride, redset_hip_plan** out) {
+  if (!rs) return fail("null rs state");
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(parity),
+                              rs->ranks, chunk_size, stride, out))
+    return rc;
+  std::vector<StripeMap> maps(rs->ranks);
+  for (int c = 0; c < rs->ranks; ++c) redset_hip::rs_verify_map(rs, c, maps[c]);
+  return finish_verify_crc_plan(REDSET_HIP_PLAN_RS_VERIFY_CRC32, rs->ranks, rs->encoding, chunk_size, stride, maps,
+                                SetLayout{lofi, parity, stride}, rs, out);
+}
+
+int redset_hip_xor_plan_verify_crc32(int ranks, unsigned char* const* lofi, unsigned char* const* xorc,
+                                     size_t chunk_size, size_t stride, redset_hip_plan** out) {
+  if (ranks < 2) return fail("XOR needs at least 2 ranks, got %d", ranks);
+  if (int rc = check_set_args(reinterpret_cast<const void* const*>(lofi), reinterpret_cast<const void* const*>(xorc),
+                              ranks, chunk_size, stride, out))
+    return rc;
+  std::vector<StripeMap> maps(ranks);
+  for (int c = 0; c < ranks; ++c) redset_hip::xor_encode_map(ranks, c, maps[c]);
+  return finish_verify_crc_plan(REDSET_HIP_PLAN_XOR_VERIFY_CRC32, ranks, 1, chunk_size, stride, maps,
+                                SetLayout{lofi, xorc, stride}, nullptr, out);
+}
+
+int redset_hip_plan_verify_crc32_report(const redset_hip_plan* plan, void* stream, unsigned* crcs, int ncrcs) {
+  if (!plan || !crcs) return fail("verify_crc32_report: null argument");
+  if (!is_verify_crc(plan)) return fail("verify_crc32_report: not a verify + CRC plan (kind %d)", plan->info.kind);
+  const int n = plan->ver_crc.finish.nranges;
+  if (ncrcs < n) return fail("verify_crc32_report: room for %d CRCs, the plan reports %d", ncrcs, n);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = hip_check(hipMemcpyAsync(crcs, plan->ver_crc.finish.crcs, static_cast<size_t>(n) * sizeof(unsigned),
+                                        hipMemcpyDeviceToHost, s),
+                         "verify_crc32 report copy"))
+    return rc;
+  return hip_check(hipStreamSynchronize(s), "verify_crc32 report sync");
 }
 
 int redset_hip_rs_plan_repair(const redset_hip_rs* rs, unsigned char* const* lofi, unsigned char* const* parity,
@@ -1950,6 +2099,8 @@ int redset_hip_plan_execute(const redset_hip_plan* plan, void* stream) {
     return hip_check(static_cast<hipError_t>(redset_hip::launch_crc32(plan->crc, stream)), "crc32 launch");
   if (is_encode_crc(plan))
     return hip_check(static_cast<hipError_t>(redset_hip::launch_encode_crc(plan->enc_crc, stream)), "encode_crc launch");
+  if (is_verify_crc(plan))
+    return hip_check(static_cast<hipError_t>(redset_hip::launch_verify_crc(plan->ver_crc, stream)), "verify_crc launch");
   if (plan->info.kind == REDSET_HIP_PLAN_RS_REPAIR) {
     if (int e = redset_hip::launch_repair_reset(plan->repair, stream))
       return hip_check(static_cast<hipError_t>(e), "repair report reset");
